@@ -14,11 +14,23 @@ Workload = BASELINE.json configs[1]: 4096 rays x 64 samples per GPU, T=2^16 hash
 branch on a second stream.  N GPUs: weak scaling, every rank renders its own 4096 rays (global batch 4096*N);
 --union-batch = the N ranks share one 4096-ray batch (strong).
 
-Prints ONE JSON line (rank 0) with `roofline` (the kernel with the largest summed duration: algorithmic bytes or flops /
-its duration, from the library's own event pair around every kernel launch on the launch stream -- dns_kernel_timing --
-over K eagerly launched steps of the same workload; a replayed graph cannot be bracketed per kernel), `kernel_rooflines`
-(the same for every kernel), `iteration_roofline` (whole iteration incl. PMC traffic per step) and `cpu_baseline` (the
-oracle, PyTorch CPU, on this host's cores, bounded sample).
+Prints ONE JSON line (rank 0): the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall
+time of the K timed steps / K) and `iteration_roofline` (whole iteration incl. PMC traffic per step).  A plain run does only
+that: set up, warm up, time the K steps (eager, two streams, unless --graph / --no-overlap say otherwise), write the outputs
+(--dump-outputs DIR), print the line.  --full adds everything that takes runs of its own: the launch-mode trial (eager vs
+hipGraph replay, the faster one runs the timed region), `step_ms_spread`, `roofline` (the kernel with the largest summed
+duration: algorithmic bytes or flops / its duration, from the library's own event pair around every kernel launch on the
+launch stream -- dns_kernel_timing -- over K eagerly launched steps of the same workload; a replayed graph cannot be
+bracketed per kernel), `kernel_rooflines` (the same for every kernel), the `render_forward` / `tracking` /
+`reference_precision` lines and `cpu_baseline` (the oracle, PyTorch CPU, on this host's cores, bounded sample).
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed -- its loss terms, the parameters it left
+(networks, hash table, poses) and its gradients -- as DIR/<name>.npy (float32; an array above DUMP_MAX_ELEMS as a fixed seeded
+sample of its elements).  The same arguments give the last timed step the same inputs on every run: its draws come from the
+seeded generator in a fixed order (with --full: as long as the launch trial picks the same mode), and its parameters, poses and optimiser state are the seeded initial ones, restored from
+a copy taken at setup just before that step (one device copy inside the timed region, with --dump-outputs only).  The steps
+before it sum some gradients with floating-point atomics, and Adam with pose optimisation would carry that rounding through
+every later step; from restored inputs the outputs agree to rounding.
 """
 import argparse
 import math
@@ -252,6 +264,8 @@ def build(wl, device, seed, dist_ctx, overlap=False, graph=False, prefetch=None,
             return ms.out[6]                 # the ray-batch loss (a view: no launch); ms.losses() adds the smoothness term
 
         return cfg, bound, cam, frames, mapper, step
+
+    mapper.bench_poses, mapper.bench_optimizer = (quad_list, T_list), optimizer
 
     def step():
         if buckets is not None:
@@ -494,20 +508,92 @@ def launch_ranks(n_gpus, argv):
     return relay_rank0_line(cmd, n_gpus, env)
 
 
+DUMP_MAX_ELEMS = 1 << 22        # elements per array written by --dump-outputs (16 MB of float32); larger arrays: a seeded sample
+DUMP_MAX_BYTES = 64 * 10 ** 6   # the whole dump
+
+
+def step_state(mapper):
+    """Every tensor a step reads and the optimiser step rewrites: parameters, poses, Adam moments and step count."""
+    ms = getattr(mapper, "map_step", None)
+    if ms is not None:
+        nets = [ms.p_table, ms.p_coarse, ms.p_color, ms.p_logit, ms.p_pool] + ([ms.p_merge] if ms.stem else [])
+        return nets + [ms.Q, ms.T, ms.M, ms.V, ms.adam_state]
+    opt = mapper.bench_optimizer
+    params = [p for g in opt.param_groups for p in g["params"]]
+    return params + [t for p in params for t in opt.state[p]] + [opt._dev_state]
+
+
+def step_outputs(mapper, last):
+    """What the last step computed, as its caller receives it: the loss and its terms, the parameters the optimiser step left
+    (networks, hash table, poses), the step's gradients and the rendered depth / colour of its rays.  {name: tensor}."""
+    ms = getattr(mapper, "map_step", None)
+    out = {}
+    if ms is not None:
+        total, terms = ms.losses()
+        order = ("p_loss", "d_loss", "l_loss", "lt_loss", "fs_loss", "opacity_loss", "smooth_loss")
+        out["loss"] = total.reshape(1)
+        out["loss_terms"] = torch.stack([terms[k].reshape(()) for k in order if k in terms])
+        names = ["table", "coarse", "color", "logit", "pool"] + (["merge"] if ms.stem else [])
+        for n in names:
+            out["param_" + n] = getattr(ms, "p_" + n)
+            out["grad_" + n] = getattr(ms, "g_" + n)
+        out["param_quat"], out["param_trans"] = ms.Q, ms.T
+        out["grad_quat"], out["grad_trans"] = ms.g_quat, ms.g_trans
+        out["render_depth"], out["render_rgb"] = ms.depth, ms.rgb
+        return out
+    # the autograd driver (--autograd-step): the loss it returned, the optimiser's parameters and their gradients
+    out["loss"] = last.detach().reshape(1)
+    named = list(mapper.decoder.named_parameters()) + [("fine_pool", mapper.fine_decoders.pool)]
+    quads, Ts = mapper.bench_poses
+    named += [(f"quat_{k}", q) for k, q in enumerate(quads)] + [(f"trans_{k}", t) for k, t in enumerate(Ts)]
+    for n, p in named:
+        n = n.replace(".", "_")
+        out["param_" + n] = p.detach()
+        if p.grad is not None:
+            out["grad_" + n] = p.grad
+    return out
+
+
+def dump_outputs(path, arrays):
+    """``arrays`` as path/<name>.npy in float32.  An array above DUMP_MAX_ELEMS elements is written as the same seeded
+    sample of its flattened elements on every run (sorted indices of numpy's default_rng(0))."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes at {name}")
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: launch-mode trial, per-step spread, per-kernel rooflines, the "
+                         "render / tracking / reference-precision lines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel timing pass")
     ap.add_argument("--verbose", action="store_true", help="per-step progress on stderr")
-    ap.add_argument("--no-render-forward", action="store_true", help="skip the secondary full-image render line")
+    ap.add_argument("--no-render-forward", action="store_true",
+                    help="with --full: skip the secondary render / tracking / reference-precision lines")
     ap.add_argument("--graph", action="store_true",
                     help="replay the iteration from a hipGraph on one stream (slower than the eager two-stream default, see capture())")
     ap.add_argument("--eager", "--no-graph", dest="eager", action="store_true",
-                    help="(default) launch the iteration eagerly, the smoothness branch on a second stream")
+                    help="(the default of a plain run) launch the iteration eagerly, the smoothness branch on a second stream; "
+                         "with --full: skip the launch-mode trial")
     ap.add_argument("--no-overlap", action="store_true", help="eager, but keep the smoothness branch on the main stream")
     ap.add_argument("--graph-branches", action="store_true", help="with --graph: capture the smoothness branch as a parallel branch")
     ap.add_argument("--autograd-step", action="store_true",
@@ -525,6 +611,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher yet: this process becomes the parent of N ranks and touches no GPU itself
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -550,15 +638,27 @@ def main():
     # lattice captured as a branch, 2.45 without).  With the fixed launch sequence (fused_step.MapStep: 0.44 ms of host enqueue
     # per step) eager wins on every workload measured (cfg2 2.09 vs 2.28-2.34 ms, ref 1.00 vs 1.23); with the autograd driver
     # (--autograd-step: 2.0 ms of enqueue) small workloads on a slow host were HOST-bound and the graph won.  Default (neither
-    # --graph nor --eager, one GPU): both are built, timed for a few untimed steps, and the faster one runs the timed region
-    # -- reported as launch_mode / launch_trial_ms.
-    auto_mode = not args.graph and not args.eager and not args.no_overlap and ctx.world_size == 1
+    # --graph nor --eager, one GPU) with --full: both are built, timed for a few untimed steps, and the faster one runs the timed
+    # region -- reported as launch_mode / launch_trial_ms.  A plain run launches eagerly, the mode every trial of rounds 3-5
+    # picked on every workload (profiles/r0[345]_bench_*.json), after the same ten untimed settle steps the trial ends with:
+    # its step sequence, and with it what --dump-outputs writes, does not depend on a timing.
+    default_mode = not args.graph and not args.eager and not args.no_overlap and ctx.world_size == 1
+    auto_mode = default_mode and args.full
     use_graph = args.graph and not args.eager and ctx.world_size == 1
     # the smoothness branch on a second stream (eager), or -- with --graph-branches -- as a parallel branch of the captured graph
     overlap = (not use_graph or args.graph_branches) and not args.no_overlap
     union = ctx.union
     cfg, bound, cam, frames, mapper, step = build(wl, device, seed=100 + (0 if union else ctx.rank), dist_ctx=ctx, overlap=overlap,
                                                   graph=use_graph, fused_step=not args.autograd_step, stem_features=args.stem_features)
+    restore_at = -1
+    if args.dump_outputs:
+        # the seeded initial state, put back before the last timed step: that step's inputs are then the same on every run
+        state = step_state(mapper)
+        with torch.no_grad():
+            initial = [t.detach().clone() for t in state]
+            torch._foreach_copy_(state, initial)      # (a no-op here: loads the copy kernel before the clock runs, not at the restore)
+        torch.cuda.synchronize()
+        restore_at = args.steps - 1
     n_rays = 4 * sum(wl["rays"])
     job_rays = n_rays if union else n_rays * ctx.world_size          # rays the whole job renders per step
     S = wl["nu"] + wl["ns"]
@@ -617,6 +717,10 @@ def main():
             for _ in range(10):
                 step()
             torch.cuda.synchronize()
+    elif default_mode:
+        for _ in range(10):
+            step()
+        torch.cuda.synchronize()
     for i in range(args.warmup):
         tw = time.perf_counter()
         run()
@@ -634,6 +738,9 @@ def main():
     last = None
     marks = []
     for i in range(args.steps):
+        if i == restore_at:
+            with torch.no_grad():
+                torch._foreach_copy_(state, initial)
         last = run()
         if args.verbose and i % 10 == 9:
             torch.cuda.synchronize()
@@ -650,10 +757,12 @@ def main():
     if final_loss is not None and not math.isfinite(final_loss):
         raise RuntimeError(f"non-finite loss after the timed steps ({final_loss}): the measurement is void")
     elapsed = ctx.max_over_ranks(elapsed, device)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(mapper, last))
     # spread: the same K steps once more with an event pair around every step (outside the timed region; the events sit on the
     # main stream, which every step's side-stream work joins before the optimiser step)
     spread = None
-    if ctx.world_size == 1:
+    if args.full and ctx.world_size == 1:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
         for e0, e1 in evs:
             e0.record()
@@ -667,7 +776,7 @@ def main():
     # per-kernel durations for the roofline: the same K steps launched eagerly with an event pair around every
     # C-ABI call (a replayed graph cannot be bracketed per kernel; kernels and shapes are identical)
     kernel_times, spans = {}, []
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         mapper.overlap_smooth = False           # one stream: an event pair must bracket its own kernel only
         ops.timer.arm(kernels=True)             # + the library's own event pair around every kernel launch
         for _ in range(args.steps):
@@ -720,110 +829,110 @@ def main():
     out = {
         "metric": "ray-samples/s", "value": value, "unit": "ray-samples/s", "n_gpus": ctx.world_size,
         "rccl_ranks": ctx.group_size(), "dist_backend": ctx.backend_name(),
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "step_ms_spread": spread, "higher_is_better": True,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
         "scaling": "strong" if union else "weak", "vs_baseline": None, "dtype": ("f16 activations and MFMA operands, f32 accumulate, loss scale 128 (MLPs: half rows); f32 elsewhere" if wl.get("mlp_dtype") == "fp16" else
                   "f32 (MLP products as 3 x f16 split-operand MFMA / 6 x bf16 for weight gradients, f32 accumulate: error <= fp32 fma chain)"), "data": "synthetic", "hip_graph": graphed, "streams": 2 if overlap else 1, "launch_mode": "hipGraph replay" if graphed else "eager",
         "step_driver": "fixed launch sequence (fused_step.MapStep)" if getattr(mapper, "map_step", None) is not None else "torch.autograd",
-        "launch_trial_ms": trial, "final_loss": final_loss,
+        "final_loss": final_loss,
         "config": {"workload": args.workload + ": " + wl["desc"] + (" -- with --stem-features: the 2-D branch (feature_matching + "
                                 "Decoder.merge on 3 reference views per target frame) runs inside every iteration" if args.stem_features else ""), "rays_per_gpu": job_rays // ctx.world_size, "samples_per_ray": S,
                    "global_rays": job_rays,
                    "parallelism": f"dp{ctx.world_size} (" + ("strong: union batch -- rank slices of ONE shared-seed batch of "
                                                               f"{n_rays} rays and of the lattice" if union else
                                                               f"weak: {n_rays} rays per rank, one batch and one lattice per rank") + ")"},
-        "roofline": roofline,
         "iteration_roofline": iteration_roofline,
-        "kernel_rooflines": per_kernel,
-        "kernel_breakdown": breakdown,
     }
-    # secondary line: forward-only full-image render of one 640x480 frame (frame_vis path), rays/s
-    try:
-        if args.no_render_forward:
-            raise RuntimeError("skipped (--no-render-forward)")
-        mapper.static_shapes = False
-        torch.cuda.synchronize()
-        rf = lambda: mapper.render_frame(frames["gt_color"][0], frames["gt_depth"][0], frames["gt_label"][0],
-                                         frames["est_c2w"][0], n_pts_batch=65536)
-        rf()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(3):
+    if args.full:
+        out.update({"step_ms_spread": spread, "launch_trial_ms": trial, "roofline": roofline, "kernel_rooflines": per_kernel,
+                    "kernel_breakdown": breakdown})
+        # secondary line: forward-only full-image render of one 640x480 frame (frame_vis path), rays/s
+        try:
+            if args.no_render_forward:
+                raise RuntimeError("skipped (--no-render-forward)")
+            mapper.static_shapes = False
+            torch.cuda.synchronize()
+            rf = lambda: mapper.render_frame(frames["gt_color"][0], frames["gt_depth"][0], frames["gt_label"][0],
+                                             frames["est_c2w"][0], n_pts_batch=65536)
             rf()
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t1) / 3
-        out["render_forward"] = {"rays_per_s": cam["H"] * cam["W"] / dt, "ray_samples_per_s": cam["H"] * cam["W"] * S / dt,
-                                 "ms_per_frame": dt * 1e3, "what": "full 640x480 frame, forward only, 65536-ray chunks"}
-    except Exception as e:
-        out["render_forward"] = {"error": f"{type(e).__name__}: {e}"}
-    # secondary line: the tracking optimise step (slams/tracking.py:313-340), 500 rays, coarse-only render, pose-only Adam
-    try:
-        if args.no_render_forward:
-            raise RuntimeError("skipped (--no-render-forward)")
-        from dns_slam_amd.tracking import Tracker
-        tcfg = dict(cfg)
-        tracker = Tracker(tcfg, mapper.decoder, bound, cam, device=device)
-        cur = {"gt_color": frames["gt_color"][1], "gt_depth": frames["gt_depth"][1], "gt_label": frames["gt_label"][1]}
-        n_it = tcfg["tracking"]["n_iters"]
-        res = {}
-        for mode in ("eager", "graph"):
-            tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, fused=True, graph=(mode == "graph"))
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, fused=True, graph=(mode == "graph"))
+            for _ in range(3):
+                rf()
             torch.cuda.synchronize()
-            res[mode] = (time.perf_counter() - t1) * 1e3 / n_it
-        # the same loop as a fixed launch sequence (fused_step.TrackStep), eager and as one captured iteration replayed n_it times
-        tracker.use_track_step = True
-        for fused in (False, True):
-            tracker.use_fused_kernel = fused
+            dt = (time.perf_counter() - t1) / 3
+            out["render_forward"] = {"rays_per_s": cam["H"] * cam["W"] / dt, "ray_samples_per_s": cam["H"] * cam["W"] * S / dt,
+                                     "ms_per_frame": dt * 1e3, "what": "full 640x480 frame, forward only, 65536-ray chunks"}
+        except Exception as e:
+            out["render_forward"] = {"error": f"{type(e).__name__}: {e}"}
+        # secondary line: the tracking optimise step (slams/tracking.py:313-340), 500 rays, coarse-only render, pose-only Adam
+        try:
+            if args.no_render_forward:
+                raise RuntimeError("skipped (--no-render-forward)")
+            from dns_slam_amd.tracking import Tracker
+            tcfg = dict(cfg)
+            tracker = Tracker(tcfg, mapper.decoder, bound, cam, device=device)
+            cur = {"gt_color": frames["gt_color"][1], "gt_depth": frames["gt_depth"][1], "gt_label": frames["gt_label"][1]}
+            n_it = tcfg["tracking"]["n_iters"]
+            res = {}
             for mode in ("eager", "graph"):
-                tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, graph=(mode == "graph"))
+                tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, fused=True, graph=(mode == "graph"))
                 torch.cuda.synchronize()
                 t1 = time.perf_counter()
-                for _ in range(3):
-                    tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, graph=(mode == "graph"))
+                tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, fused=True, graph=(mode == "graph"))
                 torch.cuda.synchronize()
-                res[("fused_" if fused else "step_") + mode] = (time.perf_counter() - t1) * 1e3 / (3 * n_it)
-        out["tracking"] = {"ms_per_iter_eager": res["eager"], "ms_per_iter_graph_incl_capture": res["graph"],
-                           "ms_per_iter_track_step_eager": res["step_eager"],
-                           "ms_per_iter_track_step_graph": res["step_graph"],       # the tracker keeps its TrackStep: capture paid once, by the first frame
-                           # round 5: the iteration as ONE kernel + a pose kernel (2 launches; csrc/track_fused.inc), incl. the frame's
-                           # up-front draws and dns_track_fused_begin
-                           "ms_per_iter_fused_eager": res["fused_eager"], "ms_per_iter_fused_graph": res["fused_graph"],
-                           "launches_per_iter_fused": 2,
-                           "rays": tcfg["tracking"]["n_pixels"], "samples_per_ray": S, "iters_per_frame": n_it}
-    except Exception as e:
-        out["tracking"] = {"error": f"{type(e).__name__}: {e}"}
-    # secondary line: the same shapes with the networks in the REFERENCE's own precision (tcnn: f16 activations / weights, loss
-    # scale 128 -- models/decoder.py:58-64,94; half rows, ABI v12).  Not the headline: `value` above keeps the fp32-grade networks
-    # that BASELINE's 1e-4 parity asks for.  One GPU, the default workload only; skipped with --no-render-forward.
-    skip16 = args.no_render_forward or ctx.world_size != 1 or args.workload != "cfg2" or args.stem_features or args.autograd_step
-    try:
-        if skip16:
-            raise StopIteration
-        wl16 = WORKLOADS["cfg2_fp16"]
-        _, _, _, _, mapper16, step16 = build(wl16, device, seed=1000, dist_ctx=ctx, overlap=True, graph=False)
-        for _ in range(50):
-            step16()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        n16 = 200
-        for _ in range(n16):
-            step16()
-        torch.cuda.synchronize()
-        dt16 = (time.perf_counter() - t1) / n16
-        l16 = float(step16().detach())
-        if not math.isfinite(l16):
-            raise RuntimeError("non-finite loss")
-        out["reference_precision"] = {"workload": "cfg2_fp16", "ms_per_step": dt16 * 1e3, "ray_samples_per_s": 4 * sum(wl16["rays"]) * S / dt16,
-                                      "dtype": "f16 activations and MFMA operands, f32 accumulate, loss scale 128 (half rows, ABI v12)",
-                                      "half_rows": bool(mapper16.map_step.half), "steps": n16, "final_loss": l16,
-                                      "what": "cfg2's shapes, the MLPs in tcnn's own precision; eager, two streams; a secondary line"}
-        del mapper16, step16
-    except StopIteration:
-        pass                                                  # (not this run's leg: more than one rank / another workload / --no-render-forward)
-    except Exception as e:
-        out["reference_precision"] = {"error": f"{type(e).__name__}: {e}"}
+                res[mode] = (time.perf_counter() - t1) * 1e3 / n_it
+            # the same loop as a fixed launch sequence (fused_step.TrackStep), eager and as one captured iteration replayed n_it times
+            tracker.use_track_step = True
+            for fused in (False, True):
+                tracker.use_fused_kernel = fused
+                for mode in ("eager", "graph"):
+                    tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, graph=(mode == "graph"))
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    for _ in range(3):
+                        tracker.track_frame(cur, frames["est_c2w"][1], n_iters=n_it, graph=(mode == "graph"))
+                    torch.cuda.synchronize()
+                    res[("fused_" if fused else "step_") + mode] = (time.perf_counter() - t1) * 1e3 / (3 * n_it)
+            out["tracking"] = {"ms_per_iter_eager": res["eager"], "ms_per_iter_graph_incl_capture": res["graph"],
+                               "ms_per_iter_track_step_eager": res["step_eager"],
+                               "ms_per_iter_track_step_graph": res["step_graph"],       # the tracker keeps its TrackStep: capture paid once, by the first frame
+                               # round 5: the iteration as ONE kernel + a pose kernel (2 launches; csrc/track_fused.inc), incl. the frame's
+                               # up-front draws and dns_track_fused_begin
+                               "ms_per_iter_fused_eager": res["fused_eager"], "ms_per_iter_fused_graph": res["fused_graph"],
+                               "launches_per_iter_fused": 2,
+                               "rays": tcfg["tracking"]["n_pixels"], "samples_per_ray": S, "iters_per_frame": n_it}
+        except Exception as e:
+            out["tracking"] = {"error": f"{type(e).__name__}: {e}"}
+        # secondary line: the same shapes with the networks in the REFERENCE's own precision (tcnn: f16 activations / weights, loss
+        # scale 128 -- models/decoder.py:58-64,94; half rows, ABI v12).  Not the headline: `value` above keeps the fp32-grade networks
+        # that BASELINE's 1e-4 parity asks for.  One GPU, the default workload only; skipped with --no-render-forward.
+        skip16 = args.no_render_forward or ctx.world_size != 1 or args.workload != "cfg2" or args.stem_features or args.autograd_step
+        try:
+            if skip16:
+                raise StopIteration
+            wl16 = WORKLOADS["cfg2_fp16"]
+            _, _, _, _, mapper16, step16 = build(wl16, device, seed=1000, dist_ctx=ctx, overlap=True, graph=False)
+            for _ in range(50):
+                step16()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            n16 = 200
+            for _ in range(n16):
+                step16()
+            torch.cuda.synchronize()
+            dt16 = (time.perf_counter() - t1) / n16
+            l16 = float(step16().detach())
+            if not math.isfinite(l16):
+                raise RuntimeError("non-finite loss")
+            out["reference_precision"] = {"workload": "cfg2_fp16", "ms_per_step": dt16 * 1e3, "ray_samples_per_s": 4 * sum(wl16["rays"]) * S / dt16,
+                                          "dtype": "f16 activations and MFMA operands, f32 accumulate, loss scale 128 (half rows, ABI v12)",
+                                          "half_rows": bool(mapper16.map_step.half), "steps": n16, "final_loss": l16,
+                                          "what": "cfg2's shapes, the MLPs in tcnn's own precision; eager, two streams; a secondary line"}
+            del mapper16, step16
+        except StopIteration:
+            pass                                                  # (not this run's leg: more than one rank / another workload / --no-render-forward)
+        except Exception as e:
+            out["reference_precision"] = {"error": f"{type(e).__name__}: {e}"}
     if args.loop > 0 and ctx.world_size == 1:
         try:
             mapper.overlap_smooth, mapper.prefetch_draws = True, True
@@ -831,7 +940,7 @@ def main():
             out["slam_loop"] = slam_loop(cfg, bound, cam, frames, mapper, step, device, args.loop)
         except Exception as e:
             out["slam_loop"] = {"error": f"{type(e).__name__}: {e}"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(wl, cfg, bound, cam, frames)
         except Exception as e:                               # never lose the GPU line to a host-side problem

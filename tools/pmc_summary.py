@@ -49,7 +49,7 @@ def load(d):
 
 
 fe, wr = load(fetch_dir), load(write_dir)
-# iterations actually profiled = launches of the optimiser kernel (bench.py runs warm-up + timed + a per-step spread pass)
+# iterations actually profiled = launches of the optimiser kernel (bench.py runs warm-up + timed steps; --full adds a spread pass)
 if "adam_step_kernel" in fe or "adam_step_kernel" in wr:
     n_steps = max(fe.get("adam_step_kernel", [0])[0], wr.get("adam_step_kernel", [0])[0]) or n_steps
 kern = {}
