@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class DnsGridMeta(C.Structure):
@@ -122,6 +122,11 @@ SIGNATURES = {
     "dns_adam_step": (C.c_int, [C.POINTER(DnsAdamTensor), _U, C.c_float, C.c_float, C.c_float, _P, _P]),
     "dns_composite_fwd": (C.c_int, [_P, _P, _P, _U, _U, _U, _P, _P, _P, _P, _P, _P]),
     "dns_composite_bwd": (C.c_int, [_P, _P, _P, _U, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dns_mc_ws_bytes": (C.c_uint64, [_U, _U, _U]),
+    "dns_mc_count": (C.c_int, [_P, _U, _U, _U, C.c_float, _P, _P, _P]),
+    "dns_mc_emit": (C.c_int, [_P, _U, _U, _U, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_uint64, _P,
+                              C.c_uint64, _P]),
+    "dns_keyframe_project": (C.c_int, [_P, _U, _P, _U, _P, _P, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
 }
 
 

@@ -614,12 +614,14 @@ class Mapper:
 
     # ------------------------------------------------------------------ slams/meshing.py:461-503
     @torch.no_grad()
-    def eval_points(self, pts, pixel_pts=None, gt_label_pts=None, stage="fine", n_pts_batch=1 << 20):
+    def eval_points(self, pts, pixel_pts=None, gt_label_pts=None, stage="fine", n_pts_batch=1 << 20, rule_chunk=None):
         """``Mesher.eval_points`` (the meshing / evaluation query; decoders = this mapper's): world points [P,3] ->
         (values [P,4] = sigmoid colour + occupancy logit, -100 outside the open bound; labels [P] = argmax of the logit
         network, -1 outside; ``None`` for ``stage='coarse'``).  ``gt_label_pts`` routes the fine decoders exactly like
         the reference (an unknown class raises ValueError, classes with a single point give zeros).  Forward only; runs
-        in chunks of ``n_pts_batch`` points (the reference's marching-cubes driver sends 500 000 at a time)."""
+        in chunks of ``n_pts_batch`` points (the reference's marching-cubes driver sends 500 000 at a time).  ``rule_chunk``: the
+        > 1 point rule counts per ``rule_chunk`` consecutive points instead of per call -- one call with ``rule_chunk=B`` gives
+        what one call per B-point chunk gives (Mesher's vertex query, meshing.py:739-747)."""
         dev = self.device
         pts = pts.to(dev).float()
         P = pts.shape[0]
@@ -633,8 +635,7 @@ class Mapper:
                 (p64[:, 2] < b[2, 1]) & (p64[:, 2] > b[2, 0]))
         if classes is not None:
             slot_all = self._class_slots(classes, True)       # unknown class -> ValueError, like meshing.py:451
-            # the > 1 point rule is per CALL in the reference: count over all points, not per chunk
-            cnt_all = torch.bincount(slot_all.clamp_min(0), minlength=max(len(self.fine_decoders), 1))
+            routed = self._routed_slots(slot_all, rule_chunk)
         values, labels = [], []
         n_code = 0 if pixel_pts is None else pixel.shape[1]
         fused = getattr(self, "fused_nets", True) and self.pe_dim % 4 == 0 and self.pe_dim <= 64 and \
@@ -660,8 +661,7 @@ class Mapper:
                     pool = self.fine_decoders
                     pool_p, n_g = pool.pool, max(len(pool), 1)
                     shp_f = (self.pe_dim + self.grid_dim, self.hidden_dim + 1, pool.nn_, pool.nl)
-                    sl = slot_all[s0:s1]
-                    slot = torch.where((sl >= 0) & (cnt_all[sl.clamp_min(0)] > 1), sl, torch.full_like(sl, -1))
+                    slot = routed[s0:s1]
                     fp16 = getattr(dec.coarse_fn.decoder, "fp16", False)
                 code = torch.empty(s1 - s0, 0, device=dev) if pixel_pts is None else pixel[s0:s1]
                 _, _, raw, logits = ops.render_nets(buf, code, dec.coarse_fn.decoder.params, pool_p, dec.out_fn.color_decoder.params,
@@ -678,9 +678,7 @@ class Mapper:
                 lat = self.decoder.coarse_fn(pe, features=grid_pts)
             else:
                 pool = self.fine_decoders
-                cnt = cnt_all
-                slot = torch.where((slot_all[s0:s1] >= 0) & (cnt[slot_all[s0:s1].clamp_min(0)] > 1), slot_all[s0:s1],
-                                   torch.full_like(slot_all[s0:s1], -1))
+                slot = routed[s0:s1]
                 lat = ops.mlp_grouped(fused_cat(pe, grid_pts), pool.pool[:max(len(pool), 1)], slot, self.pe_dim + self.grid_dim,
                                       self.hidden_dim + 1, pool.nn_, pool.nl, min_count=1, fp16=getattr(pool, "fp16", False))
             color, logits = self.decoder.out_fn(pe, torch.cat((lat[:, 1:], pixel[s0:s1]), -1))
@@ -694,6 +692,49 @@ class Mapper:
         labels = torch.cat(labels) if len(labels) != 1 else labels[0]
         labels[~mask] = -1
         return values, labels
+
+    def _routed_slots(self, slot_all, rule_chunk=None):
+        """Pool row of every point, -1 where its class has a single point (meshing.py:455: ``index.sum() > 1``).  The count is
+        per call (``rule_chunk`` None) or per ``rule_chunk`` consecutive points: one key chunk * n_slots + slot, one bincount."""
+        n = max(len(self.fine_decoders), 1)
+        if rule_chunk is None:
+            cnt = torch.bincount(slot_all.clamp_min(0), minlength=n)
+            ok = cnt[slot_all.clamp_min(0)] > 1
+        else:
+            key = torch.arange(slot_all.numel(), device=slot_all.device) // int(rule_chunk) * n + slot_all.clamp_min(0)
+            ok = torch.bincount(key)[key] > 1
+        return torch.where((slot_all >= 0) & ok, slot_all, torch.full_like(slot_all, -1))
+
+    @torch.no_grad()
+    def eval_occupancy(self, pts, gt_label_pts=None, stage="fine", n_pts_batch=1 << 22, rule_chunk=None):
+        """``eval_points(pts, None, gt_label_pts, stage)[0][:, 3]`` without the colour / logit networks (the marching-cubes grid
+        pass reads only the occupancy, meshing.py:620,654): the encoder plus the coarse network or the class-routed fine
+        networks.  [P] fp32 occupancy logits, -100 outside the open bound.  ``rule_chunk`` as in ``eval_points``."""
+        dev = self.device
+        pts = pts.to(dev).float()
+        P = pts.shape[0]
+        if stage != "coarse" and gt_label_pts is None:
+            raise ValueError("eval_occupancy(stage='fine') needs gt_label_pts")
+        if stage != "coarse":
+            routed = self._routed_slots(self._class_slots(gt_label_pts.to(dev).long().reshape(-1), True), rule_chunk)
+        pool, dec = self.fine_decoders, self.decoder
+        occ = torch.empty(P, device=dev)
+        for s0 in range(0, P, n_pts_batch):
+            s1 = min(s0 + n_pts_batch, P)
+            buf = dec.pe_fn.forward_world(pts[s0:s1], self.bound)
+            if stage == "coarse":
+                lat = dec.coarse_fn(buf[:, :self.pe_dim], features=buf[:, self.pe_dim:])
+            else:
+                lat = ops.mlp_grouped(buf, pool.pool[:max(len(pool), 1)], routed[s0:s1], self.pe_dim + self.grid_dim,
+                                      self.hidden_dim + 1, pool.nn_, pool.nl, min_count=1,
+                                      fp16=getattr(dec.coarse_fn.decoder, "fp16", False))
+            occ[s0:s1] = lat[:, 0]
+        b = self.bound_dev
+        p64 = pts.to(torch.float64)
+        mask = ((p64[:, 0] < b[0, 1]) & (p64[:, 0] > b[0, 0]) & (p64[:, 1] < b[1, 1]) & (p64[:, 1] > b[1, 0]) &
+                (p64[:, 2] < b[2, 1]) & (p64[:, 2] > b[2, 0]))
+        occ[~mask] = -100
+        return occ
 
     # ------------------------------------------------------------------ slams/mapping.py:638-724 (without the plotting)
     @torch.no_grad()

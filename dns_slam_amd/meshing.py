@@ -1,0 +1,194 @@
+"""Semantic mesh extraction: reference ``Mesher`` (slams/meshing.py:17-784) on this package's mapper.
+
+The grid query, the keyframe projection and marching cubes run on the GPU (csrc/mesh.hip, ``Mapper.eval_occupancy``); the
+reference's host-side numpy / skimage / trimesh steps have no counterpart here beyond the binary PLY writer below.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+class Mesher:
+    """``Mesher(cfg, slam)`` of the reference for one ``mapping.Mapper``.  Reads ``cfg['meshing']`` (resolution, level_set,
+    points_batch_size, clean_mesh), ``cfg['scale']`` (default 1) and ``cfg['back_end']['marching_cubes_bound']`` (default:
+    the mapper's bound)."""
+
+    def __init__(self, cfg: dict, mapper):
+        m = cfg["meshing"]
+        self.mapper = mapper
+        self.device = mapper.device
+        self.resolution = int(m["resolution"])
+        self.level_set = float(m["level_set"])
+        self.points_batch_size = int(m["points_batch_size"])
+        self.clean_mesh = bool(m.get("clean_mesh", True))
+        self.scale = float(cfg.get("scale", 1))
+        if m.get("depth_test", False):
+            raise NotImplementedError("Mesher: depth_test=True (point_masks' rendered-depth test) is not supported")
+        if m.get("get_largest_components", False):
+            raise NotImplementedError("Mesher: get_largest_components needs a connected-components pass (not supported)")
+        mcb = cfg.get("back_end", {}).get("marching_cubes_bound")
+        self.marching_cubes_bound = (np.array(mcb, dtype=np.float64) * self.scale if mcb is not None
+                                     else mapper.bound.detach().cpu().numpy().astype(np.float64))
+        self.cam = {"fx": mapper.fx, "fy": mapper.fy, "cx": mapper.cx, "cy": mapper.cy}
+
+    # ------------------------------------------------------------------ meshing.py:535-559
+    def get_grid_uniform(self, resolution=None):
+        """The axes of the query grid: float64 linspace over the bound padded by 0.05, ``resolution`` samples per axis.  The
+        points themselves are made on the device per chunk (``grid_points``), in the reference's meshgrid order."""
+        n = self.resolution if resolution is None else int(resolution)
+        b, pad = self.marching_cubes_bound, 0.05
+        return {"xyz": [np.linspace(b[a][0] - pad, b[a][1] + pad, n) for a in range(3)]}
+
+    def grid_points(self, xyz, s0, s1):
+        """Points s0..s1 of the reference's flattened meshgrid (indexing 'xy': point (j nx + i) nz + k = (x_i, y_j, z_k)),
+        fp32 as ``torch.tensor(..., dtype=torch.float)`` rounds them."""
+        x, y, z = (torch.tensor(a, dtype=torch.float64, device=self.device).float() for a in xyz)
+        nx, nz = x.numel(), z.numel()
+        n = torch.arange(s0, s1, device=self.device)
+        return torch.stack((x[(n // nz) % nx], y[n // (nx * nz)], z[n % nz]), 1)
+
+    def _keyframes(self, keyframe_dict):
+        dev = self.device
+        c2w = torch.stack([torch.as_tensor(kf["est_c2w"]).to(dev) for kf in keyframe_dict])
+        w2c = torch.inverse(c2w).float()                                     # meshing.py:208,319
+        labels = torch.stack([torch.as_tensor(kf["gt_label"]).to(dev).float() for kf in keyframe_dict])
+        max_depth = torch.stack([torch.as_tensor(kf["gt_depth"]).to(dev).float().max() for kf in keyframe_dict])
+        return w2c, labels, max_depth
+
+    def _check_supported(self):
+        if getattr(self.mapper, "encoder", None) is not None:
+            raise NotImplementedError("Mesher: a mapper with stem features (mapper.encoder set) needs get_2d_feature's 2-D codes "
+                                      "through Merge, which this mesher does not compute")
+
+    @torch.no_grad()
+    def grid_occupancy(self, keyframe_dict, stage="fine", kf=None):
+        """[nx, ny, nz] occupancy volume of the query grid (meshing.py:643-654: keyframe labels -> eval_points per
+        points_batch_size chunk -> values[:, 3]) and the grid's axes."""
+        self._check_supported()
+        kf = kf or self._keyframes(keyframe_dict)
+        grid = self.get_grid_uniform()
+        nx, ny, nz = (len(a) for a in grid["xyz"])
+        P = nx * ny * nz
+        B = self.points_batch_size
+        step = B * max(1, (1 << 22) // B)                     # device chunks on points_batch_size boundaries
+        occ = torch.empty(P, device=self.device)
+        for s0 in range(0, P, step):
+            s1 = min(s0 + step, P)
+            pts = self.grid_points(grid["xyz"], s0, s1)
+            label = None
+            if stage != "coarse":
+                label, _ = ops.keyframe_project(pts, kf[0], kf[1], kf[2], self.cam)
+            occ[s0:s1] = self.mapper.eval_occupancy(pts, label, stage=stage, rule_chunk=B)
+        return occ.reshape(ny, nx, nz).permute(1, 0, 2).contiguous(), grid
+
+    @torch.no_grad()
+    def extract(self, keyframe_dict, stage="fine", clean_mesh=True):
+        """-> (verts [V,3] fp32 world / scale, faces [F,3] int32, colors [V,3] uint8, labels [V] int64), all on the device."""
+        self._check_supported()
+        kf = self._keyframes(keyframe_dict)
+        vol, grid = self.grid_occupancy(keyframe_dict, stage, kf)
+        x, y, z = grid["xyz"]
+        verts, faces = ops.marching_cubes(vol, self.level_set, (x[0], y[0], z[0]), (x[2] - x[1], y[2] - y[1], z[2] - z[1]))
+        if clean_mesh and faces.shape[0]:
+            verts, faces = self.clean(verts, faces, kf)
+        colors, labels = self.vertex_query(verts, kf, stage)
+        return verts / self.scale, faces, colors, labels
+
+    def clean(self, verts, faces, kf):
+        """meshing.py:714-719: drop the faces whose three vertices no keyframe sees, then the vertices no face uses."""
+        _, seen = ops.keyframe_project(verts, kf[0], kf[1], kf[2], self.cam)
+        faces = faces[seen[faces.long()].any(1)]
+        used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+        used[faces.reshape(-1).long()] = True
+        new_id = torch.cumsum(used, 0, dtype=torch.int64) - 1
+        return verts[used], new_id[faces.long()].to(torch.int32)
+
+    def vertex_query(self, verts, kf, stage="fine"):
+        """meshing.py:735-753: colours (clip(rgb, 0, 1) * 255 as uint8) and labels (argmax, -1 outside the bound) at the
+        vertices, the > 1 point rule per points_batch_size chunk of vertices."""
+        if verts.shape[0] == 0:
+            return (torch.zeros(0, 3, dtype=torch.uint8, device=verts.device), torch.zeros(0, dtype=torch.int64, device=verts.device))
+        label, _ = ops.keyframe_project(verts, kf[0], kf[1], kf[2], self.cam)
+        values, labels = self.mapper.eval_points(verts, None, label, stage=stage, rule_chunk=self.points_batch_size)
+        colors = (values[:, :3].clamp(0, 1) * 255).to(torch.uint8)
+        if labels is None:
+            labels = torch.full((verts.shape[0],), -1, dtype=torch.int64, device=verts.device)
+        return colors, labels
+
+    def get_mesh(self, mesh_out_file, keyframe_dict, idx, color=True, label=False, palette=None, show_forecast=False,
+                 element=False, clean_mesh=None, stage="fine", remove_small_geometry=False, fill_holes=False):
+        """Writes ``{mesh_out_file}/mesh_{idx}.ply`` (vertex colours when ``color``, the vertex labels as an int property) and,
+        with ``label`` and a ``palette`` (class -> RGB: an [n_class, 3] array, a dict or a callable like the reference's
+        v_map_function), ``mesh_{idx}_semantic.ply``.  Returns the paths written.  The component filters and fill_holes of the
+        reference (meshing.py:721-733,759) are not implemented and are refused when asked for."""
+        if show_forecast:
+            raise NotImplementedError("Mesher.get_mesh: show_forecast is not supported")
+        if element:
+            raise NotImplementedError("Mesher.get_mesh: element (per-class meshes) is not supported")
+        if remove_small_geometry or fill_holes:
+            raise NotImplementedError("Mesher.get_mesh: small-component removal and fill_holes need a connected-components pass "
+                                      "(not supported)")
+        verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh)
+        v, f, lab = verts.cpu().numpy(), faces.cpu().numpy(), labels.cpu().numpy()
+        os.makedirs(mesh_out_file, exist_ok=True)
+        out = [os.path.join(mesh_out_file, f"mesh_{idx}.ply")]
+        write_ply(out[0], v, f, colors.cpu().numpy() if color else None, lab)
+        if label and palette is not None:
+            out.append(os.path.join(mesh_out_file, f"mesh_{idx}_semantic.ply"))
+            write_ply(out[1], v, f, label_colors(lab, palette), lab)
+        return out
+
+
+def label_colors(labels, palette):
+    """uint8 [V,3] colours of the labels through a class -> RGB palette (array, dict or callable); unknown classes black."""
+    labels = np.asarray(labels)
+    if callable(palette):
+        rgb = np.stack([np.asarray(c) for c in palette(labels)], -1) if labels.size else np.zeros((0, 3))
+        return np.asarray(rgb).reshape(-1, 3).astype(np.uint8)
+    if isinstance(palette, dict):
+        n = max(int(k) for k in palette) + 1 if palette else 0
+        table = np.zeros((n, 3), np.uint8)
+        for k, c in palette.items():
+            table[int(k)] = c
+    else:
+        table = np.asarray(palette, dtype=np.uint8).reshape(-1, 3)
+    out = np.zeros((labels.shape[0], 3), np.uint8)
+    ok = (labels >= 0) & (labels < table.shape[0])
+    out[ok] = table[labels[ok]]
+    return out
+
+
+def write_ply(path, verts, faces, colors=None, labels=None):
+    """Binary little-endian PLY 1.0: vertex ``float x, y, z`` (+ ``uchar red, green, blue``) (+ ``int label``), face
+    ``list uchar int vertex_indices``."""
+    verts = np.asarray(verts, np.float32).reshape(-1, 3)
+    faces = np.asarray(faces, np.int32).reshape(-1, 3)
+    V = verts.shape[0]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    props = ["property float x", "property float y", "property float z"]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    if labels is not None:
+        fields += [("label", "<i4")]
+        props += ["property int label"]
+    vd = np.empty(V, dtype=fields)
+    vd["x"], vd["y"], vd["z"] = verts[:, 0], verts[:, 1], verts[:, 2]
+    if colors is not None:
+        c = np.asarray(colors, np.uint8).reshape(-1, 3)
+        vd["red"], vd["green"], vd["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    if labels is not None:
+        vd["label"] = np.asarray(labels).astype(np.int32)
+    fd = np.empty(faces.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    fd["n"], fd["i"] = 3, faces
+    header = "\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {V}", *props,
+                        f"element face {faces.shape[0]}", "property list uchar int vertex_indices", "end_header"]) + "\n"
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vd.tobytes())
+        f.write(fd.tobytes())

@@ -901,3 +901,55 @@ def feature_gather(pts: torch.Tensor, refer_w2c: torch.Tensor, K, feat_nhwc: tor
     check(lib.dns_feature_gather(ptr(pts), ptr(w2c), Kh, ptr(feat_nhwc), R, P, Cc, h, w, H, W, ptr(code), ptr(mask),
                                  stream_ptr()), "dns_feature_gather")
     return code, mask.bool()
+
+
+# ----------------------------------------------------------------------------- mesh extraction (csrc/mesh.hip)
+def marching_cubes(volume: torch.Tensor, level: float, origin, spacing):
+    """volume [nx, ny, nz] fp32 (C order; volume[i,j,k] at origin + (i,j,k) * spacing), level, origin / spacing 3 floats each
+    -> (verts [V,3] fp32, faces [F,3] int32): skimage.measure.marching_cubes' shared-vertex mesh with gradient_direction=
+    'descent' (meshing.py:668-688), vertex and face order as include/dns_hip.h states.  One host read (the two totals)."""
+    vol = volume.detach().contiguous().float()
+    require_cuda(vol)
+    if vol.dim() != 3:
+        raise ValueError(f"marching_cubes: volume must be [nx, ny, nz], got {tuple(vol.shape)}")
+    nx, ny, nz = (int(s) for s in vol.shape)
+    o = (C.c_double * 3)(*[float(v) for v in origin])
+    s = (C.c_double * 3)(*[float(v) for v in spacing])
+    if not all(np.isfinite(list(s))) or not all(np.isfinite(list(o))):
+        raise ValueError("marching_cubes: origin and spacing must be finite")
+    dev = vol.device
+    ws_b = int(_rawlib.dns_mc_ws_bytes(nx, ny, nz)) if vol.numel() else 0
+    if vol.numel() and ws_b == 0:
+        raise ValueError(f"marching_cubes: grid {nx} x {ny} x {nz} is too large (>= 2^31 edges)")
+    ws = torch.empty(max(ws_b, 1), dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    check(lib.dns_mc_count(ptr(vol), nx, ny, nz, float(level), ptr(ws), ptr(totals), stream_ptr()), "dns_mc_count")
+    V, F = (int(v) for v in totals.cpu().tolist())
+    verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    if V or F:
+        check(lib.dns_mc_emit(ptr(vol), nx, ny, nz, float(level), o, s, ptr(ws), ptr(verts), V, ptr(faces), F, stream_ptr()),
+              "dns_mc_emit")
+    return verts, faces
+
+
+def keyframe_project(points: torch.Tensor, w2c: torch.Tensor, labels: torch.Tensor, max_depth: torch.Tensor, cam: dict):
+    """points [P,3] world, w2c [K,4,4] (torch.inverse(est_c2w) in fp32), labels [K,H,W] (gt_label), max_depth [K] (max of each
+    keyframe's gt_depth), cam {'fx','fy','cx','cy'} -> (label [P] fp32: get_2d_feature's label_pts, meshing.py:313-373;
+    seen [P] bool: point_masks' seen mask without the depth test, meshing.py:203-274)."""
+    pts = points.detach().contiguous().float()
+    w = w2c.detach().contiguous().float()            # torch.inverse of a batch returns column-major matrices
+    lab = labels.detach().contiguous().float()
+    md = max_depth.detach().contiguous().float().reshape(-1)
+    require_cuda(pts, w, lab, md)
+    K = int(w.shape[0])
+    if w.shape[1:] != (4, 4) or lab.dim() != 3 or lab.shape[0] != K or md.numel() != K:
+        raise ValueError("keyframe_project: w2c [K,4,4], labels [K,H,W], max_depth [K]")
+    H, W = int(lab.shape[1]), int(lab.shape[2])
+    intr = (C.c_float * 4)(float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]))
+    P = pts.shape[0]
+    label = torch.empty(P, device=pts.device)
+    seen = torch.empty(P, dtype=torch.uint8, device=pts.device)
+    check(lib.dns_keyframe_project(ptr(pts), P, ptr(w), K, ptr(lab), ptr(md), H, W, intr, ptr(label), ptr(seen), stream_ptr()),
+          "dns_keyframe_project")
+    return label, seen.bool()

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 12
+#define DNS_ABI_VERSION 13
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -605,6 +605,35 @@ int dns_refer_poses(const float* quat, const float* trans, const int32_t* src, c
 int dns_merge_dy(float* d_code, uint32_t ld_dcode, uint32_t C, uint32_t R, uint32_t pts_per_frame, const float* z,
                  const float* gt_depth, uint32_t N, uint32_t S, float* d_lat, void* stream);
 int dns_add_ref_sum(const float* d_rel, uint32_t R, uint32_t pts_per_frame, uint32_t P, float* d_pts, void* stream);
+
+/* ---- mesh extraction (Mesher.get_mesh, slams/meshing.py:562-784; csrc/mesh.hip; ABI v13) ------------------------------
+ * Marching cubes (replaces skimage.measure.marching_cubes, meshing.py:668-688) on a dense volume vol [nx, ny, nz] fp32, C order,
+ * vol[i,j,k] the value at origin + (i,j,k) * spacing.  A corner is inside iff v > level.  One vertex per grid edge whose ends
+ * straddle the level, at p0 + t (p1 - p0), t = (level - v0) / (v1 - v0) (fp32 t, fp64 positions, stored fp32); vertices are
+ * ordered by the edge index 3 * (C-order index of the edge's lower end) + axis.  Faces int32 [F,3], ordered by cube (C order of
+ * its lowest corner), then table order (csrc/mc_table.hpp, generated by tools/gen_mc_table.py), wound so that the right-hand
+ * normal points from inside (high values) to outside (skimage's gradient_direction='descent').  Grids of >= 2^31 edges and
+ * non-finite origin / spacing are refused.
+ *   dns_mc_ws_bytes: bytes of workspace for an nx x ny x nz grid (0: refused size).
+ *   dns_mc_count: the counts and their scan into ws; totals [2] uint64 (device) = (V, F).  The caller reads totals back to size
+ *     the outputs.
+ *   dns_mc_emit: with the ws of dns_mc_count on the same volume and level: verts [v_cap, 3], faces [f_cap, 3]; nothing is
+ *     written past either capacity.  origin, spacing: [host] 3 doubles each. */
+uint64_t dns_mc_ws_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int dns_mc_count(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, void* ws, uint64_t* totals, void* stream);
+int dns_mc_emit(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, const double* origin, const double* spacing,
+                const void* ws, float* verts, uint64_t v_cap, int32_t* faces, uint64_t f_cap, void* stream);
+
+/* Keyframe projection of P world points pts [P,3] into K keyframes: w2c [K,16] row-major (torch.inverse(est_c2w), fp32),
+ * labels [K,H,W] fp32 (gt_label), max_depth [K] (max of each keyframe's gt_depth), intr [host] (fx, fy, cx, cy).  The projection
+ * of both reference loops: cam = w2c @ [p,1], x *= -1, uv = K cam, z = cam_z + 1e-8, uv /= z; keyframe k sees p iff 0 < u < W,
+ * 0 < v < H, z < 0.
+ *   label [P] fp32: get_2d_feature's label_pts (meshing.py:313-373): the label at the rounded (half to even), clamped pixel of the
+ *     LAST keyframe that sees p; 0 if none does.
+ *   seen [P] uint8: point_masks' seen mask without the depth test (meshing.py:203-274, depth_test False): some keyframe sees p
+ *     and -cam_z < 1.2 max_depth[k]. */
+int dns_keyframe_project(const float* pts, uint32_t P, const float* w2c, uint32_t K, const float* labels, const float* max_depth,
+                         int H, int W, const float* intr, float* label, uint8_t* seen, void* stream);
 
 #ifdef __cplusplus
 }
