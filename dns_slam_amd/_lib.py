@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class DnsGridMeta(C.Structure):
@@ -127,6 +127,8 @@ SIGNATURES = {
     "dns_mc_emit": (C.c_int, [_P, _U, _U, _U, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_uint64, _P,
                               C.c_uint64, _P]),
     "dns_keyframe_project": (C.c_int, [_P, _U, _P, _U, _P, _P, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
+    "dns_mesh_cc_ws_bytes": (C.c_uint64, [_U]),
+    "dns_mesh_components": (C.c_int, [_P, _U, _P, _U, _P, _P, _P, _P, _P]),
 }
 
 

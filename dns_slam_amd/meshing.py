@@ -1,7 +1,8 @@
 """Semantic mesh extraction: reference ``Mesher`` (slams/meshing.py:17-784) on this package's mapper.
 
-The grid query, the keyframe projection and marching cubes run on the GPU (csrc/mesh.hip, ``Mapper.eval_occupancy``); the
-reference's host-side numpy / skimage / trimesh steps have no counterpart here beyond the binary PLY writer below.
+The grid query, the keyframe projection, marching cubes and the connected-components filter run on the GPU (csrc/mesh.hip,
+csrc/mesh_cc.hip, ``Mapper.eval_occupancy``); the reference's host-side numpy / skimage / trimesh steps have no counterpart
+here beyond the binary PLY writer below.
 """
 from __future__ import annotations
 
@@ -15,8 +16,12 @@ from . import ops
 
 class Mesher:
     """``Mesher(cfg, slam)`` of the reference for one ``mapping.Mapper``.  Reads ``cfg['meshing']`` (resolution, level_set,
-    points_batch_size, clean_mesh), ``cfg['scale']`` (default 1) and ``cfg['back_end']['marching_cubes_bound']`` (default:
-    the mapper's bound)."""
+    points_batch_size, clean_mesh, remove_small_geometry_threshold), ``cfg['scale']`` (default 1) and
+    ``cfg['back_end']['marching_cubes_bound']`` (default: the mapper's bound).
+
+    The reference always filters the cleaned mesh by connected components; here that is asked for per call: a reference config
+    with ``clean_mesh: True`` maps onto ``get_mesh(..., components="small")`` (threshold ``remove_small_geometry_threshold *
+    scale * scale``), one with ``get_largest_components: True`` onto ``components="largest"``."""
 
     def __init__(self, cfg: dict, mapper):
         m = cfg["meshing"]
@@ -27,10 +32,13 @@ class Mesher:
         self.points_batch_size = int(m["points_batch_size"])
         self.clean_mesh = bool(m.get("clean_mesh", True))
         self.scale = float(cfg.get("scale", 1))
+        thr = m.get("remove_small_geometry_threshold")
+        self.remove_small_geometry_threshold = None if thr is None else float(thr)
         if m.get("depth_test", False):
             raise NotImplementedError("Mesher: depth_test=True (point_masks' rendered-depth test) is not supported")
         if m.get("get_largest_components", False):
-            raise NotImplementedError("Mesher: get_largest_components needs a connected-components pass (not supported)")
+            raise NotImplementedError("Mesher: get_largest_components in the config is not read; pass components=\"largest\" to "
+                                      "get_mesh / extract")
         mcb = cfg.get("back_end", {}).get("marching_cubes_bound")
         self.marching_cubes_bound = (np.array(mcb, dtype=np.float64) * self.scale if mcb is not None
                                      else mapper.bound.detach().cpu().numpy().astype(np.float64))
@@ -87,26 +95,57 @@ class Mesher:
         return occ.reshape(ny, nx, nz).permute(1, 0, 2).contiguous(), grid
 
     @torch.no_grad()
-    def extract(self, keyframe_dict, stage="fine", clean_mesh=True):
-        """-> (verts [V,3] fp32 world / scale, faces [F,3] int32, colors [V,3] uint8, labels [V] int64), all on the device."""
+    def extract(self, keyframe_dict, stage="fine", clean_mesh=True, components=None, min_area=None):
+        """-> (verts [V,3] fp32 world / scale, faces [F,3] int32, colors [V,3] uint8, labels [V] int64), all on the device.
+        ``components``: None, "small" (keep the components whose area exceeds ``min_area``, default
+        ``cfg['meshing']['remove_small_geometry_threshold'] * scale * scale``) or "largest" (meshing.py:721-733); the filter
+        runs on the cleaned mesh, ahead of the vertex query, and only with ``clean_mesh``."""
         self._check_supported()
+        if components not in (None, "small", "largest"):
+            raise ValueError(f"Mesher.extract: components must be None, 'small' or 'largest', got {components!r}")
+        if components is not None and not clean_mesh:
+            raise ValueError("Mesher.extract: components needs clean_mesh=True (the reference filters only the cleaned mesh)")
+        if components == "small" and min_area is None:
+            if self.remove_small_geometry_threshold is None:
+                raise ValueError("Mesher.extract: components='small' needs cfg['meshing']['remove_small_geometry_threshold'] "
+                                 "(or min_area=)")
+            min_area = self.remove_small_geometry_threshold * self.scale * self.scale
         kf = self._keyframes(keyframe_dict)
         vol, grid = self.grid_occupancy(keyframe_dict, stage, kf)
         x, y, z = grid["xyz"]
         verts, faces = ops.marching_cubes(vol, self.level_set, (x[0], y[0], z[0]), (x[2] - x[1], y[2] - y[1], z[2] - z[1]))
         if clean_mesh and faces.shape[0]:
             verts, faces = self.clean(verts, faces, kf)
+        if components == "small":
+            verts, faces = self.filter_components(verts, faces, min_area=min_area)
+        elif components == "largest":
+            verts, faces = self.filter_components(verts, faces, largest=True)
         colors, labels = self.vertex_query(verts, kf, stage)
         return verts / self.scale, faces, colors, labels
 
     def clean(self, verts, faces, kf):
         """meshing.py:714-719: drop the faces whose three vertices no keyframe sees, then the vertices no face uses."""
         _, seen = ops.keyframe_project(verts, kf[0], kf[1], kf[2], self.cam)
-        faces = faces[seen[faces.long()].any(1)]
-        used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
-        used[faces.reshape(-1).long()] = True
-        new_id = torch.cumsum(used, 0, dtype=torch.int64) - 1
-        return verts[used], new_id[faces.long()].to(torch.int32)
+        return compact_mesh(verts, faces, seen[faces.long()].any(1))[:2]
+
+    def filter_components(self, verts, faces, min_area=None, largest=False):
+        """meshing.py:721-733 on the device (ops.mesh_components): keep the faces of the connected components whose area is
+        ``> min_area`` (strict, as in the reference), or with ``largest`` those of the component of maximum area (ties: the
+        component with the smallest face).  ``verts`` are in the scaled units ``extract`` works in, before the division by
+        ``scale``.  Faces and vertices keep their original order -- trimesh's split + concatenate lists them component by
+        component instead; the set of faces is the same -- and an empty result is the empty mesh [0,3], [0,3] (the reference
+        crashes there)."""
+        if (min_area is None) == (not largest):
+            raise ValueError("Mesher.filter_components: pass min_area or largest=True (one of them)")
+        if faces.shape[0] == 0:
+            return verts[:0], faces[:0]
+        comp, comp_area, _ = ops.mesh_components(verts, faces)
+        if largest:
+            best = comp_area.max()
+            keep = comp == comp[comp_area == best].min()
+        else:
+            keep = comp_area > float(min_area)
+        return compact_mesh(verts, faces, keep)[:2]
 
     def vertex_query(self, verts, kf, stage="fine"):
         """meshing.py:735-753: colours (clip(rgb, 0, 1) * 255 as uint8) and labels (argmax, -1 outside the bound) at the
@@ -121,19 +160,25 @@ class Mesher:
         return colors, labels
 
     def get_mesh(self, mesh_out_file, keyframe_dict, idx, color=True, label=False, palette=None, show_forecast=False,
-                 element=False, clean_mesh=None, stage="fine", remove_small_geometry=False, fill_holes=False):
+                 element=False, clean_mesh=None, stage="fine", remove_small_geometry=False, fill_holes=False, components=None,
+                 min_area=None):
         """Writes ``{mesh_out_file}/mesh_{idx}.ply`` (vertex colours when ``color``, the vertex labels as an int property) and,
         with ``label`` and a ``palette`` (class -> RGB: an [n_class, 3] array, a dict or a callable like the reference's
-        v_map_function), ``mesh_{idx}_semantic.ply``.  Returns the paths written.  The component filters and fill_holes of the
-        reference (meshing.py:721-733,759) are not implemented and are refused when asked for."""
+        v_map_function), ``mesh_{idx}_semantic.ply``.  Returns the paths written.  ``components`` / ``min_area``: the
+        connected-components filter of ``extract`` (meshing.py:721-733).  fill_holes (meshing.py:770) is not implemented and,
+        like the reference's own spellings of the filters and of the per-class meshes, refused when asked for."""
         if show_forecast:
             raise NotImplementedError("Mesher.get_mesh: show_forecast is not supported")
         if element:
-            raise NotImplementedError("Mesher.get_mesh: element (per-class meshes) is not supported")
-        if remove_small_geometry or fill_holes:
-            raise NotImplementedError("Mesher.get_mesh: small-component removal and fill_holes need a connected-components pass "
-                                      "(not supported)")
-        verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh)
+            raise NotImplementedError("Mesher.get_mesh: element is not a keyword here; the per-class meshes are written by "
+                                      "Mesher.get_part_meshes")
+        if remove_small_geometry:
+            raise NotImplementedError("Mesher.get_mesh: remove_small_geometry is not a keyword here; pass components=\"small\" "
+                                      "(or components=\"largest\")")
+        if fill_holes:
+            raise NotImplementedError("Mesher.get_mesh: fill_holes is not supported")
+        verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh,
+                                                    components, min_area)
         v, f, lab = verts.cpu().numpy(), faces.cpu().numpy(), labels.cpu().numpy()
         os.makedirs(mesh_out_file, exist_ok=True)
         out = [os.path.join(mesh_out_file, f"mesh_{idx}.ply")]
@@ -142,6 +187,32 @@ class Mesher:
             out.append(os.path.join(mesh_out_file, f"mesh_{idx}_semantic.ply"))
             write_ply(out[1], v, f, label_colors(lab, palette), lab)
         return out
+
+    def get_part_meshes(self, mesh_out_file, keyframe_dict, idx, color=True, stage="fine", clean_mesh=None, components=None,
+                        min_area=None):
+        """The reference's ``element`` branch (meshing.py:786-825): for every distinct vertex label e of the extracted mesh,
+        the faces with at least one vertex labelled e, compacted, as ``{mesh_out_file}/mesh_{idx}_part_{int(e)}.ply``.  Colours
+        and labels are those of the full mesh's vertex query, not queried again per part.  Returns the paths written."""
+        verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh,
+                                                    components, min_area)
+        os.makedirs(mesh_out_file, exist_ok=True)
+        out = []
+        for e in torch.unique(labels).tolist():
+            v, f, used = compact_mesh(verts, faces, (labels == e)[faces.long()].any(1))
+            out.append(os.path.join(mesh_out_file, f"mesh_{idx}_part_{int(e)}.ply"))
+            write_ply(out[-1], v.cpu().numpy(), f.cpu().numpy(), colors[used].cpu().numpy() if color else None,
+                      labels[used].cpu().numpy())
+        return out
+
+
+def compact_mesh(verts, faces, keep):
+    """The faces with ``keep`` [F] bool set and the vertices they use, both in their original order and the faces re-indexed,
+    plus the bool [V] mask of those vertices."""
+    faces = faces[keep]
+    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+    used[faces.reshape(-1).long()] = True
+    new_id = torch.cumsum(used, 0, dtype=torch.int64) - 1
+    return verts[used], new_id[faces.long()].to(torch.int32), used
 
 
 def label_colors(labels, palette):

@@ -953,3 +953,36 @@ def keyframe_project(points: torch.Tensor, w2c: torch.Tensor, labels: torch.Tens
     check(lib.dns_keyframe_project(ptr(pts), P, ptr(w), K, ptr(lab), ptr(md), H, W, intr, ptr(label), ptr(seen), stream_ptr()),
           "dns_keyframe_project")
     return label, seen.bool()
+
+
+# ----------------------------------------------------------------------------- mesh components (csrc/mesh_cc.hip)
+def mesh_components(verts: torch.Tensor, faces: torch.Tensor):
+    """verts [V,3] fp32, faces [F,3] int32 (any triangle list with shared vertex indices) -> (comp [F] int32: the smallest
+    face index of the face's component, comp_area [F] float64: the area of the face's component, n_comp int).  Components as
+    mesh.split(only_watertight=False) forms them (meshing.py:722): faces joined through the edges exactly two faces hold
+    (include/dns_hip.h).  A vertex index outside [0, V) raises ValueError.  One host read (the count and the index flag)."""
+    v = verts.detach().contiguous().float()
+    f = faces.detach().contiguous()
+    require_cuda(v, f)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"mesh_components: verts [V,3] and faces [F,3], got {tuple(v.shape)} and {tuple(f.shape)}")
+    if f.dtype != torch.int32:
+        raise ValueError(f"mesh_components: faces must be int32, got {f.dtype}")
+    V, F = int(v.shape[0]), int(f.shape[0])
+    dev = f.device
+    comp = torch.empty(F, dtype=torch.int32, device=dev)
+    comp_area = torch.empty(F, dtype=torch.float64, device=dev)
+    if F == 0:
+        return comp, comp_area, 0
+    ws_b = int(_rawlib.dns_mesh_cc_ws_bytes(F))
+    if ws_b == 0:
+        raise ValueError(f"mesh_components: {F} faces are too many (>= 2^29)")
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    check(lib.dns_mesh_components(ptr(v), V, ptr(f), F, ptr(ws), ptr(comp), ptr(comp_area), ptr(status), stream_ptr()),
+          "dns_mesh_components")
+    n_comp, bad = (int(x) for x in status.cpu().tolist())
+    if bad:
+        raise ValueError(f"mesh_components: a face holds a vertex index outside [0, {V})" if bad & 1 else
+                         f"mesh_components: edge table overflow (status {bad:#x})")
+    return comp, comp_area, n_comp

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 13
+#define DNS_ABI_VERSION 14
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -634,6 +634,23 @@ int dns_mc_emit(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float l
  *     and -cam_z < 1.2 max_depth[k]. */
 int dns_keyframe_project(const float* pts, uint32_t P, const float* w2c, uint32_t K, const float* labels, const float* max_depth,
                          int H, int W, const float* intr, float* label, uint8_t* seen, void* stream);
+
+/* ---- mesh components (mesh.split(only_watertight=False) of slams/meshing.py:721-733; csrc/mesh_cc.hip; ABI v14) ----------
+ * Connected components of the faces of a triangle list faces [F,3] int32 over verts [V,3] fp32, under trimesh's face_adjacency:
+ * of the 3F undirected edges (min(a,b), max(a,b)), a key that occurs exactly twice joins the two faces that hold it (nothing if
+ * both occurrences are in one face); a key that occurs once (boundary) or three or more times (non-manifold) joins nothing, and
+ * neither does a shared vertex.  Any triangle list is accepted, not only dns_mc_emit's.
+ *   dns_mesh_cc_ws_bytes: bytes of workspace for F faces (84 per face: a 4F-slot edge table of 20 bytes per slot and the
+ *     union-find parents); 0: refused size (F = 0 needs none, F >= 2^29 is refused).
+ *   dns_mesh_components: comp [F] int32 = the smallest face index of the face's component (independent of scheduling);
+ *     comp_area [F] float64 = the total area of the face's component, a face's area being 0.5 |(v1 - v0) x (v2 - v0)| in float64
+ *     from the fp32 positions (the order of the float64 sum is not fixed: run-to-run differences of a relative F 2^-53);
+ *     status [2] uint32 (device): status[0] = the number of components, status[1] = 0, or non-zero if some face holds a vertex
+ *     index outside [0, V) -- such an index is never dereferenced, the face joins nothing and has area 0, and the caller must
+ *     treat the outputs as invalid.  The caller reads status back.  F = 0: nothing is launched and nothing is written. */
+uint64_t dns_mesh_cc_ws_bytes(uint32_t F);
+int dns_mesh_components(const float* verts, uint32_t V, const int32_t* faces, uint32_t F, void* ws, int32_t* comp, double* comp_area,
+                        uint32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,10 @@
 """Mesher.extract at 256^3 with 50 keyframes on the synthetic room: ms per phase (grid query, keyframe projection, marching
-cubes, vertex query, PLY write), plus the marching cubes and the keyframe projection alone.
+cubes, clean, component filter, vertex query, PLY write), plus the marching cubes and the keyframe projection alone, and the
+component pass against its host yardstick (scipy.sparse.csgraph.connected_components on the same mesh) and against a
+device sort of the 3F edge keys (the first step of the sort-based alternative to the edge table).
 
-    python tools/time_mesh.py [--res 256] [--kf 50] [--reps 3] [--once]      (--once: one extraction, for a profiler run)
+    python tools/time_mesh.py [--res 256] [--kf 50] [--reps 3] [--once]      (--once: one extraction with the component
+    filter, for a profiler run)
 """
 import argparse
 import os
@@ -48,12 +51,13 @@ def main():
     mapper.set_decoder(frames)
     randomise_(dec, 1)
     randomise_([mapper.fine_decoders.pool], 2)
-    cfg["meshing"] = {"resolution": a.res, "level_set": 0.0, "points_batch_size": 16384, "clean_mesh": True}
+    cfg["meshing"] = {"resolution": a.res, "level_set": 0.0, "points_batch_size": 16384, "clean_mesh": True,
+                      "remove_small_geometry_threshold": 0.2}
     kfs = [{"est_c2w": frames["est_c2w"][i], "gt_label": frames["gt_label"][i], "gt_depth": frames["gt_depth"][i]}
            for i in range(a.kf)]
     m = Mesher(cfg, mapper)
     if a.once:
-        v, f, c, l = m.extract(kfs)
+        v, f, c, l = m.extract(kfs, components="small")
         torch.cuda.synchronize()
         print(f"extract: {v.shape[0]} vertices, {f.shape[0]} faces")
         return
@@ -70,8 +74,30 @@ def main():
     mc = lambda: ops.marching_cubes(vol, 0.0, (x[0], y[0], z[0]), (x[2] - x[1], y[2] - y[1], z[2] - z[1]))
     t_mc, (v, f) = timed(mc, reps)
     t_clean, (v1, f1) = timed(lambda: m.clean(v, f, kf), reps)
+    thr = m.remove_small_geometry_threshold * m.scale * m.scale
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    m.filter_components(v1, f1, min_area=thr)
+    torch.cuda.synchronize()
+    t_cc_cold = (time.perf_counter() - t) * 1e3
+    t_cc, (v2, f2) = timed(lambda: m.filter_components(v1, f1, min_area=thr), reps)
+    t_cc_op, (_, _, n_comp) = timed(lambda: ops.mesh_components(v1, f1), reps)
+    fa, fb = f1.long(), f1.long().roll(-1, 1)
+    t_sort, _ = timed(lambda: torch.sort(((torch.minimum(fa, fb) << 32) | torch.maximum(fa, fb)).reshape(-1)), reps)
     t_vq, (c, l) = timed(lambda: m.vertex_query(v1, kf), reps)
     t_ext, _ = timed(lambda: m.extract(kfs), reps)
+    t_ext_cc, _ = timed(lambda: m.extract(kfs, components="small"), reps)
+    import mesh_cc_ref                                       # host yardstick: numpy adjacency + scipy's connected_components
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    f1n = f1.cpu().numpy()
+    t = time.perf_counter()
+    adj = mesh_cc_ref.face_adjacency(f1n)
+    t_adj = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter()
+    n_host, _ = connected_components(coo_matrix((np.ones(len(adj), np.int8), (adj[:, 0], adj[:, 1])), shape=(len(f1n),) * 2),
+                                     directed=False)
+    t_scipy = (time.perf_counter() - t) * 1e3
     vn, fn, cn, ln = v1.cpu().numpy(), f1.cpu().numpy(), c.cpu().numpy(), l.cpu().numpy()
     with tempfile.TemporaryDirectory() as d:
         t = time.perf_counter()
@@ -89,8 +115,13 @@ def main():
     print(f"  grid query (points + projection + occ.)    {t_grid:8.2f} ms")
     print(f"  marching cubes (query volume)              {t_mc:8.2f} ms   {v.shape[0]} vertices, {f.shape[0]} faces")
     print(f"  clean (projection of the vertices + compaction) {t_clean:5.2f} ms   {v1.shape[0]} vertices, {f1.shape[0]} faces kept")
+    print(f"  components (filter, min_area {thr:g})         {t_cc:8.2f} ms   (first call {t_cc_cold:.2f} ms)   {f1.shape[0]} faces in, "
+          f"{n_comp} components, {f2.shape[0]} faces kept")
+    print(f"    ops.mesh_components alone                {t_cc_op:8.2f} ms   (sort of its {3 * f1.shape[0]} edge keys alone: {t_sort:.2f} ms)")
+    print(f"    host: numpy face adjacency {t_adj:.1f} ms + scipy connected_components {t_scipy:.1f} ms ({n_host} components)")
     print(f"  vertex query (projection + eval_points)    {t_vq:8.2f} ms")
-    print(f"  extract (all of the above, end to end)     {t_ext:8.2f} ms")
+    print(f"  extract (without the component filter)     {t_ext:8.2f} ms")
+    print(f"  extract (components='small')               {t_ext_cc:8.2f} ms")
     print(f"  PLY write                                  {t_ply:8.2f} ms")
     print(f"  marching cubes, sphere {a.res}^3 (count + scan + emit + one host read) {t_mc_s:.3f} ms   {vs.shape[0]} vertices")
 
