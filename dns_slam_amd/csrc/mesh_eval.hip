@@ -1,0 +1,502 @@
+// Mesh evaluation (the reference's eval_3d.py / cull_mesh.py): nearest reference point of every query, and the frustum test.
+//
+// dns_nearest_points: for each query the Euclidean distance to the nearest of M reference points and that point's index
+// (cKDTree(ref).query(query) of eval_3d.py:24-42), over a uniform cell grid of the reference cloud:
+//   nn_init:    cell counters, status and the bounding box words cleared.
+//   nn_box:     bounding box of the finite reference points (block reduction, six ordered-integer atomics per block) and the
+//               non-finite flags of both clouds (status[0]).
+//   nn_header:  one thread sizes the grid: about two cells per point (clouds sampled from surfaces leave most cells empty),
+//               at most 2^21, near-cubic cells; an axis of zero (or unusable) extent gets one cell and inv = 0.
+//   nn_count / nn_scan_* / nn_fill: counting sort of the points by cell (z fastest).  Integer atomics on the cell counters:
+//               with a few points per cell the adds are spread over as many addresses as there are occupied cells, and
+//               three small launches replace a device radix sort of (key, index) pairs.  The order inside a cell depends on
+//               scheduling; the query's result does not, because equal distances are decided by the smaller index.
+//   nn_query:   thread = query.  The query is clamped to the box (a projection onto a box never increases the distance to a
+//               point in the box), its cell found with the expression that assigned the points, and the cells are visited in
+//               growing Chebyshev rings, a z-row of cells being one contiguous range of the sorted points.  After ring r a
+//               point not yet seen lies, on some axis d, in a cell >= c_d + r + 1 or <= c_d - r - 1.  With t(x) = fl(fl(x - lo)
+//               * inv) the cell coordinate (monotone in x, relative error below 2^-23) such a point has t >= B = c_d + r + 1,
+//               so its distance on that axis is at least ((B - t(q)) - slack_d) * cellw_d, slack_d = 2^-21 (dim_d + 1) covering
+//               the rounding of both t and cellw_d = (1 - 2^-20) / inv rounded down; a side with no cells left bounds nothing.
+//               The search stops once best <= (min over the sides)^2.  A query that reaches max_ring rings without stopping
+//               is appended to the todo list with the best candidate it has.
+//   nn_brute:   tiled all pairs over the todo list: a workgroup holds 256 queries in registers, walks an 8192-point chunk of
+//               the reference cloud through LDS tiles and merges through a 64-bit atomicMin on (distance^2 bits, index).
+//               With DNS_NEAREST_BRUTE every query goes this way (nn_pack instead of the grid build): the baseline the grid
+//               is timed against.
+//   nn_finish:  distance and index of the todo queries from the packed minimum.
+// Every pair distance is the same fp32 expression (dx dx + dy dy + dz dz, compiled with -ffp-contract=off), and the minimum of
+// a set does not depend on the order: grid and brute force return identical distances, identical over repeated calls.
+//
+// dns_frustum_seen: check_proj of eval_3d.py:62-88 / the loop of cull_mesh.py:53-74 for all poses: thread = point, poses in
+// LDS tiles, a workgroup leaves at the first tile after which all its points are seen.
+#include <algorithm>
+#include "common.hpp"
+
+namespace dns {
+
+namespace {
+
+constexpr int NN_BLOCK = 256;
+constexpr uint32_t NN_CELLS_CAP = 1u << 21;
+constexpr int NN_SCAN_PER = 8;                                   // cells per thread of the scan kernels
+constexpr uint32_t NN_SCAN_TILE = NN_BLOCK * NN_SCAN_PER;        // 2048 cells per workgroup, at most 1024 workgroups
+constexpr int NN_SUMS_BLOCK = 1024;
+constexpr int NN_BOX_BLOCK = 1024, NN_BOX_GRID = 64;
+constexpr int NN_BRUTE_TILE = 1024;                              // reference points per LDS tile (16 KiB)
+constexpr uint32_t NN_BRUTE_CHUNK = 8192;                        // reference points per workgroup
+constexpr uint32_t NN_BRUTE_GRID_Y = 256;                        // query tiles walked with this stride
+constexpr uint32_t NN_BAD_REF = 1u, NN_BAD_QUERY = 2u;           // status[0] bits
+constexpr uint64_t NN_NONE = 0x7f800000ffffffffull;              // (+inf, no index)
+
+struct NnHeader {                                                // first 256 bytes of the workspace
+  uint32_t box[6];                                               // ordered-integer min xyz, max xyz
+  float lo[3], hi[3], inv[3], cellw[3], slack[3];
+  int32_t dim[3];
+  uint32_t n_cells;
+};
+
+struct NnWs {
+  NnHeader* head;
+  uint32_t* count;       // [cells_alloc + 1]
+  uint32_t* start;       // [cells_alloc + 1]
+  uint32_t* sums;        // [1024]
+  uint32_t* point_cell;  // [M]
+  float4* sorted;        // [M] (x, y, z, index bits)
+  uint32_t* todo;        // [N]
+  uint64_t* best;        // [N]
+  uint32_t target, cells_alloc;
+};
+
+inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+inline uint32_t cells_target(uint32_t M) {
+  const uint64_t t = 2ull * M;
+  return (uint32_t)(t < 1 ? 1 : (t > NN_CELLS_CAP ? NN_CELLS_CAP : t));
+}
+
+size_t nn_layout(void* ws, uint32_t M, uint32_t N, NnWs* w) {
+  const uint32_t target = cells_target(M);
+  const uint32_t alloc = (target + NN_SCAN_TILE - 1) / NN_SCAN_TILE * NN_SCAN_TILE;
+  char* p = (char*)ws;
+  size_t off = 0;
+  const auto take = [&](size_t bytes) {
+    char* r = p + off;
+    off += align256(bytes);
+    return r;
+  };
+  char* head = take(sizeof(NnHeader));
+  char* count = take(((size_t)alloc + 1) * 4);
+  char* start = take(((size_t)alloc + 1) * 4);
+  char* sums = take(1024 * 4);
+  char* pc = take((size_t)M * 4);
+  char* sorted = take((size_t)M * 16);
+  char* todo = take((size_t)N * 4);
+  char* best = take((size_t)N * 8);
+  if (w) {
+    w->head = (NnHeader*)head, w->count = (uint32_t*)count, w->start = (uint32_t*)start, w->sums = (uint32_t*)sums;
+    w->point_cell = (uint32_t*)pc, w->sorted = (float4*)sorted, w->todo = (uint32_t*)todo, w->best = (uint64_t*)best;
+    w->target = target, w->cells_alloc = alloc;
+  }
+  return off;
+}
+
+__device__ __forceinline__ uint32_t f2ord(float f) {
+  const uint32_t b = __float_as_uint(f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_init_kernel(NnWs w, bool grid, uint32_t* __restrict__ status) {
+  const uint32_t t = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (grid && t <= w.cells_alloc) w.count[t] = 0u;
+  if (t < 4) status[t] = 0u;
+  if (t < 3) w.head->box[t] = 0xffffffffu, w.head->box[3 + t] = 0u;
+}
+
+__global__ __launch_bounds__(NN_BOX_BLOCK) void nn_box_kernel(const float* __restrict__ ref, uint32_t M, const float* __restrict__ query,
+                                                              uint32_t N, NnHeader* __restrict__ head, uint32_t* __restrict__ status) {
+  __shared__ float s_v[6][NN_BOX_BLOCK / WAVE];
+  __shared__ uint32_t s_bad;
+  if (threadIdx.x == 0) s_bad = 0u;
+  __syncthreads();
+  const float inf = __builtin_inff();
+  float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+  uint32_t bad = 0u;
+  const uint32_t stride = gridDim.x * NN_BOX_BLOCK, t0 = blockIdx.x * NN_BOX_BLOCK + threadIdx.x;
+  for (uint32_t i = t0; i < M; i += stride) {
+    const float x = ref[3 * (size_t)i], y = ref[3 * (size_t)i + 1], z = ref[3 * (size_t)i + 2];
+    if (isfinite(x) && isfinite(y) && isfinite(z)) {
+      mn[0] = fminf(mn[0], x), mn[1] = fminf(mn[1], y), mn[2] = fminf(mn[2], z);
+      mx[0] = fmaxf(mx[0], x), mx[1] = fmaxf(mx[1], y), mx[2] = fmaxf(mx[2], z);
+    } else {
+      bad |= NN_BAD_REF;
+    }
+  }
+  for (uint32_t i = t0; i < N; i += stride) {
+    const float x = query[3 * (size_t)i], y = query[3 * (size_t)i + 1], z = query[3 * (size_t)i + 2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) bad |= NN_BAD_QUERY;
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      mn[d] = fminf(mn[d], __shfl_xor(mn[d], o));
+      mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o));
+    }
+  if (bad) atomicOr(&s_bad, bad);
+  const int lane = threadIdx.x % WAVE, wv = threadIdx.x / WAVE;
+  if (lane == 0)
+    for (int d = 0; d < 3; ++d) s_v[d][wv] = mn[d], s_v[3 + d][wv] = mx[d];
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const bool is_min = threadIdx.x < 3;
+    float v = s_v[threadIdx.x][0];
+    for (int k = 1; k < NN_BOX_BLOCK / WAVE; ++k) v = is_min ? fminf(v, s_v[threadIdx.x][k]) : fmaxf(v, s_v[threadIdx.x][k]);
+    if (is_min) {
+      if (v < inf) atomicMin(&head->box[threadIdx.x], f2ord(v));
+    } else {
+      if (v > -inf) atomicMax(&head->box[threadIdx.x], f2ord(v));
+    }
+  }
+  if (threadIdx.x == 0 && s_bad) atomicOr(&status[0], s_bad);
+}
+
+__global__ void nn_header_kernel(NnHeader* __restrict__ h, uint32_t target, uint32_t* __restrict__ status) {
+  if (threadIdx.x || blockIdx.x) return;
+  const bool ok = (status[0] & NN_BAD_REF) == 0u;
+  double ext[3], vol = 1.0;
+  bool live[3];
+  int k = 0;
+  for (int d = 0; d < 3; ++d) {
+    const float lo = ok ? ord2f(h->box[d]) : 0.f, hi = ok ? ord2f(h->box[3 + d]) : 0.f;
+    h->lo[d] = lo, h->hi[d] = hi;
+    ext[d] = (double)hi - (double)lo;
+    live[d] = ok && ext[d] >= 1e-30 && ext[d] <= 1e30;
+    if (live[d]) vol *= ext[d], ++k;
+  }
+  // near-cubic cells of volume (box volume) / target over the axes at least one cell long; a shorter axis gets one cell and
+  // leaves the product (three rounds at the most).  Rounding the counts down keeps their product at or under target.
+  double cell = 1.0;
+  for (int round = 0; round < 3 && k; ++round) {
+    cell = pow(vol / (double)target, 1.0 / k);
+    bool changed = false;
+    for (int d = 0; d < 3; ++d)
+      if (live[d] && !(ext[d] >= cell)) live[d] = false, changed = true;
+    if (!changed) break;
+    vol = 1.0, k = 0;
+    for (int d = 0; d < 3; ++d)
+      if (live[d]) vol *= ext[d], ++k;
+  }
+  int64_t dim[3];
+  for (int d = 0; d < 3; ++d) {
+    double n = live[d] && cell > 0.0 ? floor(ext[d] / cell) : 1.0;
+    n = n >= 1.0 ? n : 1.0;                                      // also a NaN
+    dim[d] = (int64_t)(n > (double)target ? (double)target : n);
+  }
+  while (dim[0] * dim[1] * dim[2] > (int64_t)target) {           // only through the rounding of pow and the quotients
+    const int a = dim[0] >= dim[1] ? (dim[0] >= dim[2] ? 0 : 2) : (dim[1] >= dim[2] ? 1 : 2);
+    --dim[a];
+  }
+  for (int d = 0; d < 3; ++d) {
+    float inv = dim[d] > 1 ? (float)((double)dim[d] / ext[d]) : 0.f;
+    if (!(inv >= 1e-30f && inv <= 1e30f)) inv = 0.f, dim[d] = 1;
+    h->inv[d] = inv;
+    h->dim[d] = (int32_t)dim[d];
+    // rounded towards zero: never above (1 - 2^-20) / inv
+    h->cellw[d] = inv > 0.f ? __double2float_rz((1.0 - 0x1p-20) / (double)inv) : 0.f;
+    h->slack[d] = (float)(dim[d] + 1) * 0x1p-21f;
+  }
+  h->n_cells = (uint32_t)(dim[0] * dim[1] * dim[2]);
+  status[2] = h->n_cells;
+}
+
+// The cell coordinate of x on one axis; the SAME expression places the points and bounds the search (two roundings: the file is
+// compiled with -ffp-contract=off).
+__device__ __forceinline__ float nn_t(float x, float lo, float inv) { return (x - lo) * inv; }
+__device__ __forceinline__ int nn_cell(float t, int dim) { return (int)fminf(fmaxf(floorf(t), 0.f), (float)(dim - 1)); }
+
+__device__ __forceinline__ uint64_t nn_pack(float4 p, float qx, float qy, float qz) {
+  const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
+  const float d2 = dx * dx + dy * dy + dz * dz;                  // >= +0, or NaN (whose bits order above +inf's)
+  return ((uint64_t)__float_as_uint(d2) << 32) | (uint64_t)__float_as_uint(p.w);
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_count_kernel(const float* __restrict__ ref, uint32_t M, NnWs w) {
+  const uint32_t i = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (i >= M) return;
+  const NnHeader* h = w.head;
+  const int cx = nn_cell(nn_t(ref[3 * (size_t)i], h->lo[0], h->inv[0]), h->dim[0]);
+  const int cy = nn_cell(nn_t(ref[3 * (size_t)i + 1], h->lo[1], h->inv[1]), h->dim[1]);
+  const int cz = nn_cell(nn_t(ref[3 * (size_t)i + 2], h->lo[2], h->inv[2]), h->dim[2]);
+  const uint32_t c = ((uint32_t)cx * (uint32_t)h->dim[1] + (uint32_t)cy) * (uint32_t)h->dim[2] + (uint32_t)cz;   // < n_cells
+  w.point_cell[i] = c;
+  atomicAdd(&w.count[c], 1u);
+}
+
+// exclusive scan of count[0 .. cells_alloc) into start: per-workgroup totals, their scan by one workgroup, the local scans
+__global__ __launch_bounds__(NN_BLOCK) void nn_scan_sums_kernel(NnWs w) {
+  __shared__ uint32_t s[NN_BLOCK / WAVE];
+  const uint32_t base = blockIdx.x * NN_SCAN_TILE + threadIdx.x * NN_SCAN_PER;
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < NN_SCAN_PER; ++k) v += w.count[base + k];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if (threadIdx.x % WAVE == 0) s[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) w.sums[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+}
+
+__global__ __launch_bounds__(NN_SUMS_BLOCK) void nn_scan_top_kernel(NnWs w, uint32_t n_blocks) {
+  __shared__ uint32_t s[NN_SUMS_BLOCK];
+  const uint32_t t = threadIdx.x;
+  const uint32_t own = t < n_blocks ? w.sums[t] : 0u;
+  s[t] = own;
+  __syncthreads();
+  for (uint32_t o = 1; o < NN_SUMS_BLOCK; o <<= 1) {
+    const uint32_t a = t >= o ? s[t - o] : 0u;
+    __syncthreads();
+    s[t] += a;
+    __syncthreads();
+  }
+  if (t < n_blocks) w.sums[t] = s[t] - own;
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_scan_local_kernel(NnWs w, uint32_t M) {
+  __shared__ uint32_t s[NN_BLOCK];
+  const uint32_t t = threadIdx.x, base = blockIdx.x * NN_SCAN_TILE + t * NN_SCAN_PER;
+  uint32_t c[NN_SCAN_PER], own = 0;
+#pragma unroll
+  for (int k = 0; k < NN_SCAN_PER; ++k) c[k] = w.count[base + k], own += c[k];
+  s[t] = own;
+  __syncthreads();
+  for (uint32_t o = 1; o < NN_BLOCK; o <<= 1) {
+    const uint32_t a = t >= o ? s[t - o] : 0u;
+    __syncthreads();
+    s[t] += a;
+    __syncthreads();
+  }
+  uint32_t run = w.sums[blockIdx.x] + s[t] - own;
+#pragma unroll
+  for (int k = 0; k < NN_SCAN_PER; ++k) {
+    w.start[base + k] = run;
+    run += c[k];
+  }
+  if (blockIdx.x == gridDim.x - 1 && t == NN_BLOCK - 1) w.start[w.cells_alloc] = M;
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_fill_kernel(const float* __restrict__ ref, uint32_t M, NnWs w) {
+  const uint32_t i = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (i >= M) return;
+  const uint32_t c = w.point_cell[i];
+  const uint32_t k = atomicSub(&w.count[c], 1u) - 1u;            // count[c] holds the cell's population once more
+  const uint32_t pos = w.start[c] + k;
+  if (pos < M) w.sorted[pos] = make_float4(ref[3 * (size_t)i], ref[3 * (size_t)i + 1], ref[3 * (size_t)i + 2], __uint_as_float(i));
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_pack_kernel(const float* __restrict__ ref, uint32_t M, uint32_t N, NnWs w,
+                                                           uint32_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (i < M) w.sorted[i] = make_float4(ref[3 * (size_t)i], ref[3 * (size_t)i + 1], ref[3 * (size_t)i + 2], __uint_as_float(i));
+  if (i < N) w.todo[i] = i, w.best[i] = NN_NONE;
+  if (i == 0) status[1] = N;
+}
+
+__device__ __forceinline__ uint64_t nn_range(const float4* __restrict__ sorted, uint32_t s, uint32_t e, float qx, float qy, float qz,
+                                             uint64_t best) {
+  for (uint32_t j = s; j < e; ++j) {
+    const uint64_t pk = nn_pack(sorted[j], qx, qy, qz);
+    best = pk < best ? pk : best;
+  }
+  return best;
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_query_kernel(NnWs w, uint32_t M, const float* __restrict__ query, uint32_t N,
+                                                            uint32_t max_ring, float* __restrict__ dist, int32_t* __restrict__ idx,
+                                                            uint32_t* __restrict__ status) {
+  const uint32_t q = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (q >= N) return;
+  const NnHeader* h = w.head;
+  const float qv[3] = {query[3 * (size_t)q], query[3 * (size_t)q + 1], query[3 * (size_t)q + 2]};
+  float t[3], slack[3], cellw[3];
+  int c[3], dim[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    dim[d] = h->dim[d], slack[d] = h->slack[d], cellw[d] = h->cellw[d];
+    t[d] = nn_t(fminf(fmaxf(qv[d], h->lo[d]), h->hi[d]), h->lo[d], h->inv[d]);     // a NaN coordinate clamps to lo
+    c[d] = nn_cell(t[d], dim[d]);
+  }
+  const uint32_t* __restrict__ start = w.start;
+  const float4* __restrict__ sorted = w.sorted;
+  uint64_t best = NN_NONE;
+  bool done = false;
+  for (uint32_t ring = 0; ring <= max_ring; ++ring) {
+    const int r = (int)ring;
+    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, dim[0] - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, dim[1] - 1);
+    const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, dim[2] - 1);
+    for (int x = x0; x <= x1; ++x)
+      for (int y = y0; y <= y1; ++y) {
+        const uint32_t row = ((uint32_t)x * (uint32_t)dim[1] + (uint32_t)y) * (uint32_t)dim[2];
+        if (abs(x - c[0]) == r || abs(y - c[1]) == r) {            // a face of the ring: the whole z-row is one range
+          best = nn_range(sorted, start[row + z0], min(start[row + z1 + 1], M), qv[0], qv[1], qv[2], best);
+        } else {                                                   // inside: the row's two end cells
+          if (c[2] - r >= 0) best = nn_range(sorted, start[row + c[2] - r], min(start[row + c[2] - r + 1], M), qv[0], qv[1], qv[2], best);
+          if (c[2] + r < dim[2]) best = nn_range(sorted, start[row + c[2] + r], min(start[row + c[2] + r + 1], M), qv[0], qv[1], qv[2], best);
+        }
+      }
+    float lb = __builtin_inff();
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int up = c[d] + r + 1, dn = c[d] - r;                  // unseen cells: >= up, < dn
+      if (up <= dim[d] - 1) lb = fminf(lb, fmaxf(((float)up - t[d]) - slack[d], 0.f) * cellw[d]);
+      if (dn >= 1) lb = fminf(lb, fmaxf((t[d] - (float)dn) - slack[d], 0.f) * cellw[d]);
+    }
+    if (__uint_as_float((uint32_t)(best >> 32)) <= lb * lb) {      // lb = inf: every cell has been seen
+      done = true;
+      break;
+    }
+  }
+  if (done) {
+    dist[q] = sqrtf(__uint_as_float((uint32_t)(best >> 32)));
+    idx[q] = (int32_t)(uint32_t)best;
+  } else {
+    const uint32_t pos = atomicAdd(&status[1], 1u);
+    if (pos < N) w.todo[pos] = q;
+    w.best[q] = best;
+  }
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_brute_kernel(NnWs w, uint32_t M, const float* __restrict__ query, uint32_t N,
+                                                            const uint32_t* __restrict__ status) {
+  __shared__ float4 tile[NN_BRUTE_TILE];
+  const uint32_t n_todo = min(status[1], N);
+  const uint32_t j0 = blockIdx.x * NN_BRUTE_CHUNK, j1 = min(j0 + NN_BRUTE_CHUNK, M);
+  for (uint32_t tq = blockIdx.y; (uint64_t)tq * NN_BLOCK < n_todo; tq += gridDim.y) {
+    const uint32_t i = tq * NN_BLOCK + threadIdx.x;
+    const bool live = i < n_todo;
+    const uint32_t q = live ? min(w.todo[i], N - 1) : 0u;
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    if (live) qx = query[3 * (size_t)q], qy = query[3 * (size_t)q + 1], qz = query[3 * (size_t)q + 2];
+    uint64_t best = NN_NONE;
+    for (uint32_t b = j0; b < j1; b += NN_BRUTE_TILE) {
+      const uint32_t n = min((uint32_t)NN_BRUTE_TILE, j1 - b);
+      __syncthreads();
+      for (uint32_t x = threadIdx.x; x < n; x += NN_BLOCK) tile[x] = w.sorted[b + x];
+      __syncthreads();
+      if (live)
+        for (uint32_t x = 0; x < n; ++x) {
+          const uint64_t pk = nn_pack(tile[x], qx, qy, qz);
+          best = pk < best ? pk : best;
+        }
+    }
+    if (live && best < __hip_atomic_load(&w.best[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMin((unsigned long long*)&w.best[q], (unsigned long long)best);
+  }
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_finish_kernel(NnWs w, uint32_t N, float* __restrict__ dist, int32_t* __restrict__ idx,
+                                                             const uint32_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (i >= min(status[1], N)) return;
+  const uint32_t q = min(w.todo[i], N - 1);
+  const uint64_t best = w.best[q];
+  dist[q] = sqrtf(__uint_as_float((uint32_t)(best >> 32)));
+  idx[q] = (int32_t)(uint32_t)best;
+}
+
+// ---- frustum test --------------------------------------------------------------------------------------------------------
+constexpr int FR_BLOCK = 256, FR_TILE = 128;                     // poses per LDS tile (12 floats each)
+
+__global__ __launch_bounds__(FR_BLOCK) void frustum_seen_kernel(const float* __restrict__ pts, uint32_t P, const float* __restrict__ w2c,
+                                                                uint32_t K, float fW, float fH, float fx, float fy, float cx, float cy,
+                                                                uint8_t* __restrict__ seen_out) {
+  __shared__ float s_w[FR_TILE * 12];
+  const uint32_t p = blockIdx.x * FR_BLOCK + threadIdx.x;
+  const bool live = p < P;
+  float px = 0.f, py = 0.f, pz = 0.f;
+  if (live) px = pts[3 * (size_t)p], py = pts[3 * (size_t)p + 1], pz = pts[3 * (size_t)p + 2];
+  bool seen = false;
+  for (uint32_t lo = 0; lo < K; lo += FR_TILE) {
+    const int n = (int)min((uint32_t)FR_TILE, K - lo);
+    __syncthreads();
+    for (int x = threadIdx.x; x < n * 12; x += FR_BLOCK) s_w[x] = w2c[(size_t)(lo + x / 12) * 16 + x % 12];
+    __syncthreads();
+    if (live && !seen) {
+      for (int kk = 0; kk < n; ++kk) {
+        const float* m = s_w + kk * 12;
+        // w2c @ [p, 1], x *= -1, K @ cam, z + 1e-5, uv / z (eval_3d.py:78-87)
+        const float cxw = m[0] * px + m[1] * py + m[2] * pz + m[3];
+        const float cyw = m[4] * px + m[5] * py + m[6] * pz + m[7];
+        const float czw = m[8] * px + m[9] * py + m[10] * pz + m[11];
+        const float z = czw + 1e-5f;
+        const float u = (fx * -cxw + cx * czw) / z;
+        const float v = (fy * cyw + cy * czw) / z;
+        if (0.f <= -z && u < fW && u > 0.f && v < fH && v > 0.f) {
+          seen = true;
+          break;
+        }
+      }
+    }
+    if (__syncthreads_and(!live || seen)) break;
+  }
+  if (live) seen_out[p] = seen ? 1 : 0;
+}
+
+}  // namespace
+
+}  // namespace dns
+
+using namespace dns;
+
+extern "C" uint64_t dns_nearest_ws_bytes(uint32_t M, uint32_t N) {
+  if (M >= (1u << 31) || N >= (1u << 31)) return 0;
+  return nn_layout(nullptr, M, N, nullptr);
+}
+
+extern "C" int dns_nearest_points(const float* ref, uint32_t M, const float* query, uint32_t N, uint32_t max_ring, uint32_t flags,
+                                  void* ws, float* dist, int32_t* idx, uint32_t* status, void* stream) {
+  DNS_REQUIRE(M < (1u << 31) && N < (1u << 31), "dns_nearest_points: %u reference points, %u queries (must be < 2^31)", M, N);
+  DNS_REQUIRE((flags & ~DNS_NEAREST_BRUTE) == 0u, "dns_nearest_points: unknown flags %#x", flags);
+  DNS_REQUIRE(max_ring <= 64u, "dns_nearest_points: max_ring %u (must be <= 64)", max_ring);
+  if (N == 0) return DNS_OK;
+  DNS_REQUIRE(M > 0, "dns_nearest_points: no reference points for %u queries", N);
+  DNS_REQUIRE(ref && query && ws && dist && idx && status, "dns_nearest_points: NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  NnWs w;
+  nn_layout(ws, M, N, &w);
+  const bool grid = !(flags & DNS_NEAREST_BRUTE);
+  const auto blocks = [](uint64_t n) { return dim3((uint32_t)((n + NN_BLOCK - 1) / NN_BLOCK)); };
+  DNS_LAUNCH(nn_init_kernel, blocks(grid ? (uint64_t)w.cells_alloc + 1 : 4), dim3(NN_BLOCK), 0, st, w, grid, status);
+  const uint32_t box_grid = (uint32_t)std::min<uint64_t>(NN_BOX_GRID, ((uint64_t)std::max(M, N) + NN_BOX_BLOCK - 1) / NN_BOX_BLOCK);
+  DNS_LAUNCH(nn_box_kernel, dim3(box_grid), dim3(NN_BOX_BLOCK), 0, st, ref, M, query, N, w.head, status);
+  if (grid) {
+    const uint32_t n_scan = w.cells_alloc / NN_SCAN_TILE;          // <= 1024
+    DNS_LAUNCH(nn_header_kernel, dim3(1), dim3(1), 0, st, w.head, w.target, status);
+    DNS_LAUNCH(nn_count_kernel, blocks(M), dim3(NN_BLOCK), 0, st, ref, M, w);
+    DNS_LAUNCH(nn_scan_sums_kernel, dim3(n_scan), dim3(NN_BLOCK), 0, st, w);
+    DNS_LAUNCH(nn_scan_top_kernel, dim3(1), dim3(NN_SUMS_BLOCK), 0, st, w, n_scan);
+    DNS_LAUNCH(nn_scan_local_kernel, dim3(n_scan), dim3(NN_BLOCK), 0, st, w, M);
+    DNS_LAUNCH(nn_fill_kernel, blocks(M), dim3(NN_BLOCK), 0, st, ref, M, w);
+    DNS_LAUNCH(nn_query_kernel, blocks(N), dim3(NN_BLOCK), 0, st, w, M, query, N, max_ring, dist, idx, status);
+  } else {
+    DNS_LAUNCH(nn_pack_kernel, blocks(std::max(M, N)), dim3(NN_BLOCK), 0, st, ref, M, N, w, status);
+  }
+  const uint32_t chunks = (M + NN_BRUTE_CHUNK - 1) / NN_BRUTE_CHUNK;
+  const uint32_t tiles = std::min(NN_BRUTE_GRID_Y, (N + NN_BLOCK - 1) / NN_BLOCK);
+  DNS_LAUNCH(nn_brute_kernel, dim3(chunks, tiles), dim3(NN_BLOCK), 0, st, w, M, query, N, (const uint32_t*)status);
+  DNS_LAUNCH(nn_finish_kernel, blocks(N), dim3(NN_BLOCK), 0, st, w, N, dist, idx, (const uint32_t*)status);
+  return check_launch("dns_nearest_points");
+}
+
+extern "C" int dns_frustum_seen(const float* pts, uint32_t P, const float* w2c, uint32_t K, int H, int W, const float* intr,
+                                uint8_t* seen, void* stream) {
+  if (P == 0) return DNS_OK;
+  DNS_REQUIRE(pts && seen && intr, "dns_frustum_seen: NULL argument");
+  DNS_REQUIRE(K == 0 || w2c, "dns_frustum_seen: K > 0 needs w2c");
+  DNS_REQUIRE(H > 0 && W > 0, "dns_frustum_seen: image %d x %d", H, W);
+  hipStream_t st = (hipStream_t)stream;
+  DNS_LAUNCH(frustum_seen_kernel, dim3((P + FR_BLOCK - 1) / FR_BLOCK), dim3(FR_BLOCK), 0, st, pts, P, w2c, K, (float)W, (float)H,
+             intr[0], intr[1], intr[2], intr[3], seen);
+  return check_launch("dns_frustum_seen");
+}

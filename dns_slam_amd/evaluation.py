@@ -1,0 +1,236 @@
+"""3-D reconstruction metrics: the reference's ``cull_mesh.py`` and ``eval_3d.py`` (calc_3d_metric) on the device.
+
+``read_ply`` / ``load_poses`` read what the tools take from disk; ``cull_mesh`` drops the faces no camera of a trajectory sees
+(``ops.frustum_seen``); ``sample_surface`` is trimesh's area-weighted surface sampler; ``accuracy`` / ``completion`` /
+``completion_ratio`` are the nearest-neighbour metrics (``ops.nearest_points`` in place of the host KD-tree) and ``metrics_3d``
+the three of them for two meshes.  The ICP alignment of the reference (open3d) is not implemented.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import ops
+from .meshing import compact_mesh
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply(path) -> dict:
+    """Binary little-endian PLY 1.0 -> {"verts": fp32 [V,3], "faces": int32 [F,3]} plus "colors" uint8 [V,3] (properties red,
+    green, blue) and "labels" int32 [V] (property label) when the file has them: what ``meshing.write_ply`` writes, and more
+    generally any scalar vertex properties of the standard PLY types in any order and a face list with a ``uchar`` count and
+    ``int`` / ``uint`` indices.  ASCII and big-endian files, faces that are not triangles and anything else this reader cannot
+    lay out raise ValueError naming the cause."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end)
+    if not data.startswith(b"ply") or end < 0 or nl < 0:
+        raise ValueError(f"read_ply: {path}: not a PLY file (no 'ply' ... 'end_header' header)")
+    lines = [l.strip() for l in data[:end].decode("ascii", "replace").splitlines()]
+    fmt = None
+    elements = []                                   # [name, count, [property, ...]]
+    for line in lines[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1:]
+        elif tok[0] == "element" and len(tok) == 3:
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property" and elements:
+            if tok[1] == "list" and len(tok) == 5:
+                elements[-1][2].append(("list", tok[4], tok[2], tok[3]))
+            elif len(tok) == 3:
+                elements[-1][2].append(("scalar", tok[2], tok[1]))
+            else:
+                raise ValueError(f"read_ply: {path}: cannot parse header line {line!r}")
+        else:
+            raise ValueError(f"read_ply: {path}: cannot parse header line {line!r}")
+    if not fmt or fmt[0] != "binary_little_endian":
+        raise ValueError(f"read_ply: {path}: format {' '.join(fmt or ['(none)'])} is not supported (binary_little_endian only; "
+                         f"ASCII and big-endian files are refused)")
+    off = nl + 1
+    vert = None
+    faces = np.zeros((0, 3), np.int32)
+    for name, count, props in elements:
+        if count < 0:
+            raise ValueError(f"read_ply: {path}: element {name} has count {count}")
+        lists = [p for p in props if p[0] == "list"]
+        for p in props:
+            for t in p[2:]:
+                if t not in _PLY_TYPES:
+                    raise ValueError(f"read_ply: {path}: unknown property type {t!r} in element {name}")
+        if name == "face":
+            if len(props) != 1 or not lists:
+                raise ValueError(f"read_ply: {path}: the face element must hold exactly one list property")
+            _, _, ct, it = props[0]
+            if _PLY_TYPES[ct] != "u1" or _PLY_TYPES[it] not in ("i4", "u4"):
+                raise ValueError(f"read_ply: {path}: face list '{ct} {it}' is not supported (uchar count, int / uint indices)")
+            rec = np.dtype([("n", "u1"), ("i", "<" + _PLY_TYPES[it], (3,))])
+            if count:
+                n0 = data[off] if off < len(data) else 3
+                if n0 != 3:
+                    raise ValueError(f"read_ply: {path}: a face has {n0} vertices; only triangles are supported")
+            if off + count * rec.itemsize > len(data):
+                raise ValueError(f"read_ply: {path}: truncated face data (or faces that are not triangles)")
+            fd = np.frombuffer(data, rec, count, off)
+            if count and not (fd["n"] == 3).all():
+                raise ValueError(f"read_ply: {path}: only triangles are supported (a face with another vertex count found)")
+            if count and _PLY_TYPES[it] == "u4" and fd["i"].max() >= 2 ** 31:
+                raise ValueError(f"read_ply: {path}: vertex index >= 2^31")
+            faces = fd["i"].astype(np.int32).reshape(-1, 3)
+            off += count * rec.itemsize
+        else:
+            if lists:
+                raise ValueError(f"read_ply: {path}: list property in element {name} is not supported")
+            rec = np.dtype([(p[1], "<" + _PLY_TYPES[p[2]]) for p in props])
+            if off + count * rec.itemsize > len(data):
+                raise ValueError(f"read_ply: {path}: truncated data in element {name}")
+            if name == "vertex":
+                vert = np.frombuffer(data, rec, count, off)
+            off += count * rec.itemsize
+    if vert is None:
+        raise ValueError(f"read_ply: {path}: no vertex element")
+    have = vert.dtype.names or ()
+    if not all(a in have for a in "xyz"):
+        raise ValueError(f"read_ply: {path}: vertex properties x, y, z are missing")
+    out = {"verts": np.stack([vert[a].astype(np.float32) for a in "xyz"], 1).reshape(-1, 3), "faces": faces}
+    if all(c in have for c in ("red", "green", "blue")):
+        out["colors"] = np.stack([vert[c].astype(np.uint8) for c in ("red", "green", "blue")], 1).reshape(-1, 3)
+    if "label" in have:
+        out["labels"] = vert["label"].astype(np.int32)
+    return out
+
+
+def load_poses(path) -> np.ndarray:
+    """Trajectory text file, 16 floats per line (a row-major camera-to-world matrix) -> float64 [K,4,4], as stored: the
+    reference's load_poses also negates columns 1 and 2, which ``cull_mesh(flip_yz=True)`` does here."""
+    poses = []
+    with open(path, "r") as f:
+        for n, line in enumerate(f):
+            tok = line.split()
+            if not tok:
+                continue
+            if len(tok) != 16:
+                raise ValueError(f"load_poses: {path}: line {n + 1} holds {len(tok)} numbers, not 16")
+            poses.append(np.array([float(t) for t in tok], np.float64).reshape(4, 4))
+    return np.stack(poses) if poses else np.zeros((0, 4, 4), np.float64)
+
+
+def world_to_camera(c2w, flip_yz=True) -> np.ndarray:
+    """c2w [K,4,4] -> fp32 [K,4,4] world-to-camera: columns 1 and 2 negated with ``flip_yz`` (cull_mesh.py:15-16,
+    eval_3d.py:68-69), inverted in float64 (np.linalg.inv, as the reference) and rounded to fp32."""
+    c = torch.as_tensor(c2w).detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w)
+    c = np.array(c, dtype=np.float64).reshape(-1, 4, 4)
+    if flip_yz:
+        c[:, :3, 1] *= -1.0
+        c[:, :3, 2] *= -1.0
+    return np.linalg.inv(c).astype(np.float32) if len(c) else np.zeros((0, 4, 4), np.float32)
+
+
+def cull_mesh(verts, faces, c2w, H, W, fx, fy, cx, cy, flip_yz=True, compact=False):
+    """cull_mesh.py: keep the faces with at least one vertex some pose of ``c2w`` [K,4,4] sees (``ops.frustum_seen``).
+    verts [V,3] fp32 and faces [F,3] int32 on the device -> (verts, faces): the vertices as they are (trimesh's update_faces),
+    or with ``compact`` only the used ones, the faces re-indexed (``meshing.compact_mesh``)."""
+    w2c = torch.from_numpy(world_to_camera(c2w, flip_yz)).to(verts.device)
+    seen = ops.frustum_seen(verts, w2c, H, W, fx, fy, cx, cy)
+    keep = seen[faces.long()].any(1) if faces.shape[0] else torch.zeros(0, dtype=torch.bool, device=verts.device)
+    if compact:
+        return compact_mesh(verts, faces, keep)[:2]
+    return verts, faces[keep]
+
+
+def _face_areas(verts, faces):
+    v = verts.detach().double()[faces.long()]
+    a, b = v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
+    nx = a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]
+    ny = a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2]
+    nz = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+    return v, 0.5 * torch.sqrt(nx * nx + ny * ny + nz * nz)
+
+
+def _sample(verts, faces, n, generator, u):
+    """sample_surface without its host read: (points, face_idx, total area as a device scalar)."""
+    if faces.dim() != 2 or faces.shape[1] != 3 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"sample_surface: verts [V,3] and faces [F,3], got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    F = int(faces.shape[0])
+    if F == 0:
+        raise ValueError("sample_surface: the mesh has no faces")
+    dev = verts.device
+    if u is None:
+        u = torch.rand(int(n), 3, dtype=torch.float64, device=dev, generator=generator)
+    else:
+        u = torch.as_tensor(u, dtype=torch.float64).to(dev)
+        if u.shape != (int(n), 3):
+            raise ValueError(f"sample_surface: u must be [{int(n)}, 3], got {tuple(u.shape)}")
+    v, area = _face_areas(verts, faces)
+    cum = torch.cumsum(area, 0)
+    total = cum[-1]
+    face = torch.searchsorted(cum, (u[:, 0] * total).contiguous(), right=False).clamp_(max=F - 1)
+    # a zero-area face is never chosen: only u0 = 0 ahead of the first face with an area could land on one; move on to that face
+    pos = torch.where(area > 0, torch.arange(F, device=dev), torch.full((F,), F - 1, device=dev))
+    face = torch.flip(torch.cummin(torch.flip(pos, (0,)), 0).values, (0,))[face]
+    r = u[:, 1:3]
+    r = torch.where((r.sum(1) > 1.0)[:, None], r - 1.0, r).abs()
+    t = v[face]
+    pts = t[:, 0] + r[:, 0:1] * (t[:, 1] - t[:, 0]) + r[:, 1:2] * (t[:, 2] - t[:, 0])
+    return pts.float(), face, total
+
+
+def sample_surface(verts, faces, n, generator=None, u=None):
+    """trimesh.sample.sample_surface (eval_3d.py:103-106): n points on the mesh, faces drawn by area.  verts [V,3] fp32, faces
+    [F,3] int32 on the device -> (points [n,3] fp32, face_idx [n] int64).  Face areas and the points are float64 (the points
+    rounded to fp32 at the end): face of sample i = searchsorted(cumsum(area), u[i,0] * total, 'left'); r = u[i,1:3], where
+    r0 + r1 > 1 r -= 1, r = |r|; point = v0 + r0 (v1 - v0) + r1 (v2 - v0).  ``u`` [n,3] float64 uniforms in [0, 1) is drawn
+    from ``generator`` on the device unless given.  Zero-area faces are never chosen; a mesh without faces or of total area 0
+    raises ValueError (one host read)."""
+    pts, face, total = _sample(verts, faces, n, generator, u)
+    if not float(total) > 0.0:
+        raise ValueError("sample_surface: the mesh has total area 0 (or a non-finite area)")
+    return pts, face
+
+
+def accuracy(gt_pts, rec_pts):
+    """eval_3d.py:31-35: mean distance from the reconstructed points to their nearest ground-truth point (float64 device
+    scalar, in the unit of the points)."""
+    return ops.nearest_points(gt_pts, rec_pts)[0].double().mean()
+
+
+def completion(gt_pts, rec_pts):
+    """eval_3d.py:38-42: mean distance from the ground-truth points to their nearest reconstructed point."""
+    return ops.nearest_points(rec_pts, gt_pts)[0].double().mean()
+
+
+def completion_ratio(gt_pts, rec_pts, dist_th=0.05):
+    """eval_3d.py:24-28: the share of ground-truth points closer than ``dist_th`` to a reconstructed point."""
+    return (ops.nearest_points(rec_pts, gt_pts)[0] < dist_th).double().mean()
+
+
+def metrics_3d(rec_verts, rec_faces, gt_verts, gt_faces, n_samples=200000, dist_th=0.05, seed=0, align=False, u_rec=None,
+               u_gt=None):
+    """calc_3d_metric (eval_3d.py:91-117) -> {"accuracy_cm", "completion_cm", "completion_ratio_pct"}: ``n_samples`` points on
+    each mesh (the reconstruction first, from one device generator seeded with ``seed``; or the uniforms ``u_rec`` / ``u_gt``),
+    two nearest-point passes, the means in float64 on the device.  One host read at the end carries the three figures and every
+    error flag.  ``align=True`` (the reference's open3d ICP, its default) is not implemented."""
+    if align:
+        raise NotImplementedError("metrics_3d: align=True (get_align_transformation, open3d's point-to-point ICP) is not "
+                                  "implemented; align the meshes beforehand")
+    dev = rec_verts.device
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    rec_pts, _, rec_area = _sample(rec_verts, rec_faces, n_samples, gen, u_rec)
+    gt_pts, _, gt_area = _sample(gt_verts, gt_faces, n_samples, gen, u_gt)
+    d_acc, _, st_acc = ops.nearest_points_launch(gt_pts, rec_pts)
+    d_comp, _, st_comp = ops.nearest_points_launch(rec_pts, gt_pts)
+    out = torch.stack((d_acc.double().mean() * 100.0, d_comp.double().mean() * 100.0,
+                       (d_comp < dist_th).double().mean() * 100.0, rec_area, gt_area, st_acc[0].double(),
+                       st_comp[0].double())).cpu().tolist()
+    if not (out[3] > 0.0 and out[4] > 0.0):
+        raise ValueError("metrics_3d: a mesh has total area 0 (or a non-finite area)")
+    if out[5] or out[6]:
+        raise ValueError("metrics_3d: non-finite coordinate in a mesh")
+    return {"accuracy_cm": out[0], "completion_cm": out[1], "completion_ratio_pct": out[2]}

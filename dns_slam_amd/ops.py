@@ -986,3 +986,71 @@ def mesh_components(verts: torch.Tensor, faces: torch.Tensor):
         raise ValueError(f"mesh_components: a face holds a vertex index outside [0, {V})" if bad & 1 else
                          f"mesh_components: edge table overflow (status {bad:#x})")
     return comp, comp_area, n_comp
+
+
+# ----------------------------------------------------------------------------- mesh evaluation (csrc/mesh_eval.hip)
+NEAREST_MAX_RINGS = 8
+
+
+def nearest_points_launch(ref: torch.Tensor, query: torch.Tensor, method: str = "grid", max_rings: int = NEAREST_MAX_RINGS):
+    """``nearest_points`` without its host read: -> (dist, idx, status [4] int32 on the device); the caller reads status
+    (include/dns_hip.h: status[0] != 0 = non-finite coordinate, the outputs invalid).  Needs N > 0."""
+    r = ref.detach().contiguous().float()
+    q = query.detach().contiguous().float()
+    require_cuda(r, q)
+    if r.dim() != 2 or r.shape[1] != 3 or q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError(f"nearest_points: ref [M,3] and query [N,3], got {tuple(r.shape)} and {tuple(q.shape)}")
+    if method not in ("grid", "brute"):
+        raise ValueError(f"nearest_points: method must be 'grid' or 'brute', got {method!r}")
+    M, N = int(r.shape[0]), int(q.shape[0])
+    if N == 0:
+        raise ValueError("nearest_points_launch: no queries")
+    if M == 0:
+        raise ValueError(f"nearest_points: no reference points for {N} queries")
+    dev = q.device
+    ws_b = int(_rawlib.dns_nearest_ws_bytes(M, N))
+    if ws_b == 0:
+        raise ValueError(f"nearest_points: {M} reference points / {N} queries are too many (>= 2^31)")
+    dist = torch.empty(N, dtype=torch.float32, device=dev)
+    idx = torch.empty(N, dtype=torch.int32, device=dev)
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    check(lib.dns_nearest_points(ptr(r), M, ptr(q), N, int(max_rings), 1 if method == "brute" else 0, ptr(ws), ptr(dist),
+                                 ptr(idx), ptr(status), stream_ptr()), "dns_nearest_points")
+    return dist, idx, status
+
+
+def nearest_points(ref: torch.Tensor, query: torch.Tensor, method: str = "grid", max_rings: int = NEAREST_MAX_RINGS,
+                   return_stats: bool = False):
+    """ref [M,3] fp32, query [N,3] fp32 -> (dist [N] fp32, idx [N] int32): for every query the Euclidean distance to the nearest
+    reference point and that point's index (``cKDTree(ref).query(query)`` of eval_3d.py:24-42; ties: the smaller index).
+    ``method``: "grid" (cell grid of the reference cloud, Chebyshev rings up to ``max_rings``, the queries left over finished by
+    the all-pairs kernel) or "brute" (the all-pairs kernel for every query); both return the same values.  ``M == 0`` with
+    queries and non-finite coordinates raise ValueError.  One host read (the status words); ``return_stats`` appends
+    ``{"brute_queries", "cells"}`` from them."""
+    if query.dim() == 2 and query.shape[0] == 0 and query.shape[1] == 3:
+        require_cuda(query)
+        out = (torch.empty(0, dtype=torch.float32, device=query.device), torch.empty(0, dtype=torch.int32, device=query.device))
+        return out + ({"brute_queries": 0, "cells": 0},) if return_stats else out
+    dist, idx, status = nearest_points_launch(ref, query, method, max_rings)
+    bad, n_brute, cells, _ = (int(x) for x in status.cpu().tolist())
+    if bad:
+        raise ValueError("nearest_points: non-finite coordinate in " + " and ".join(
+            n for b, n in ((1, "ref"), (2, "query")) if bad & b))
+    return (dist, idx, {"brute_queries": n_brute, "cells": cells}) if return_stats else (dist, idx)
+
+
+def frustum_seen(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: float, fy: float, cx: float, cy: float):
+    """points [P,3] fp32 world, w2c [K,4,4] fp32 world->camera -> seen [P] bool: some pose sees the point under check_proj of
+    eval_3d.py:62-88 (cull_mesh.py:53-74) in fp32: x = -cam.x, z' = cam.z + 1e-5, u = (fx x + cx cam.z) / z', v = (fy cam.y +
+    cy cam.z) / z'; seen iff -z' >= 0, 0 < u < W, 0 < v < H.  K = 0 sees nothing."""
+    pts = points.detach().contiguous().float()
+    w = w2c.detach().contiguous().float()
+    require_cuda(pts, w)
+    if pts.dim() != 2 or pts.shape[1] != 3 or w.dim() != 3 or w.shape[1:] != (4, 4):
+        raise ValueError(f"frustum_seen: points [P,3] and w2c [K,4,4], got {tuple(pts.shape)} and {tuple(w.shape)}")
+    P, K = int(pts.shape[0]), int(w.shape[0])
+    intr = (C.c_float * 4)(float(fx), float(fy), float(cx), float(cy))
+    seen = torch.empty(P, dtype=torch.uint8, device=pts.device)
+    check(lib.dns_frustum_seen(ptr(pts), P, ptr(w), K, int(H), int(W), intr, ptr(seen), stream_ptr()), "dns_frustum_seen")
+    return seen.bool()

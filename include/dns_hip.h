@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 14
+#define DNS_ABI_VERSION 15
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -651,6 +651,32 @@ int dns_keyframe_project(const float* pts, uint32_t P, const float* w2c, uint32_
 uint64_t dns_mesh_cc_ws_bytes(uint32_t F);
 int dns_mesh_components(const float* verts, uint32_t V, const int32_t* faces, uint32_t F, void* ws, int32_t* comp, double* comp_area,
                         uint32_t* status, void* stream);
+
+/* ---- mesh evaluation (eval_3d.py, cull_mesh.py of the reference; csrc/mesh_eval.hip; ABI v15) ---------------------------
+ * dns_nearest_points: for each of N queries query [N,3] fp32 the Euclidean distance dist [N] fp32 to the nearest of M reference
+ * points ref [M,3] fp32 and that point's index idx [N] int32 (cKDTree(ref).query(query), eval_3d.py:24-42).  Every pair
+ * distance is sqrt of the fp32 sum dx dx + dy dy + dz dz (no contraction); among equal distances the smaller index wins, so
+ * both outputs are the same for every call and both methods.  The search runs over a uniform cell grid of the reference cloud
+ * (about two cells per point, at most 2^21) in growing Chebyshev rings of cells round the query's cell, at most max_ring
+ * (<= 64) of them; the queries that could not stop by then -- in large empty regions or far outside the cloud -- are finished by
+ * a tiled all-pairs pass, so every query gets the exact answer wherever it lies.  flags = DNS_NEAREST_BRUTE sends every query
+ * through that pass and builds no grid.
+ *   dns_nearest_ws_bytes: bytes of workspace for M reference points and N queries (0: refused size, M or N >= 2^31).
+ *   status [4] uint32 (device), for the caller to read back: status[0] = 0, or bit 0 / bit 1 set if a reference / query
+ *     coordinate is not finite -- the outputs are then invalid (nothing is stored out of range); status[1] = the number of
+ *     queries the all-pairs pass finished; status[2] = the number of grid cells.
+ * N = 0: nothing is launched.  M = 0 with N > 0 is refused. */
+#define DNS_NEAREST_BRUTE 1u
+uint64_t dns_nearest_ws_bytes(uint32_t M, uint32_t N);
+int dns_nearest_points(const float* ref, uint32_t M, const float* query, uint32_t N, uint32_t max_ring, uint32_t flags, void* ws,
+                       float* dist, int32_t* idx, uint32_t* status, void* stream);
+
+/* dns_frustum_seen: seen [P] uint8 = some of the K poses w2c [K,16] (row-major world->camera, fp32) sees the point pts [P,3]:
+ * check_proj of eval_3d.py:62-88 and the loop of cull_mesh.py:53-74 in fp32: cam = w2c @ [p,1], x = -cam.x, z' = cam.z + 1e-5,
+ * u = (fx x + cx cam.z) / z', v = (fy cam.y + cy cam.z) / z'; seen iff 0 <= -z', 0 < u < W and 0 < v < H.  intr [host] (fx, fy,
+ * cx, cy).  K = 0 sees nothing. */
+int dns_frustum_seen(const float* pts, uint32_t P, const float* w2c, uint32_t K, int H, int W, const float* intr, uint8_t* seen,
+                     void* stream);
 
 #ifdef __cplusplus
 }

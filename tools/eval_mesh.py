@@ -1,0 +1,50 @@
+"""Accuracy (cm), completion (cm) and completion ratio (%) of a reconstructed mesh against a ground-truth mesh: the
+reference's eval_3d.py (calc_3d_metric without the ICP alignment), preceded by its cull_mesh.py when a trajectory is given.
+
+    python tools/eval_mesh.py --rec A.ply --gt B.ply [--traj T --H 680 --W 1200 --fx 600 --fy 600 --cx 599.5 --cy 339.5]
+                              [--n 200000] [--dist-th 0.05] [--seed 0]
+
+--traj: text file of camera-to-world poses, 16 numbers per line; the faces of --rec no pose sees are dropped first.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from dns_slam_amd import evaluation as E                     # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rec", required=True)
+    ap.add_argument("--gt", required=True)
+    ap.add_argument("--traj")
+    ap.add_argument("--H", type=int, default=680)
+    ap.add_argument("--W", type=int, default=1200)
+    ap.add_argument("--fx", type=float, default=600.0)
+    ap.add_argument("--fy", type=float, default=600.0)
+    ap.add_argument("--cx", type=float, default=599.5)
+    ap.add_argument("--cy", type=float, default=339.5)
+    ap.add_argument("--n", type=int, default=200000)
+    ap.add_argument("--dist-th", type=float, default=0.05)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    dev = "cuda:0"
+    rec, gt = E.read_ply(a.rec), E.read_ply(a.gt)
+    rv, rf = torch.from_numpy(rec["verts"]).to(dev), torch.from_numpy(rec["faces"]).to(dev)
+    gv, gf = torch.from_numpy(gt["verts"]).to(dev), torch.from_numpy(gt["faces"]).to(dev)
+    if a.traj:
+        n_faces = rf.shape[0]
+        rv, rf = E.cull_mesh(rv, rf, E.load_poses(a.traj), a.H, a.W, a.fx, a.fy, a.cx, a.cy)
+        print(f"culled {n_faces - rf.shape[0]} of {n_faces} faces", file=sys.stderr)
+    m = E.metrics_3d(rv, rf, gv, gf, n_samples=a.n, dist_th=a.dist_th, seed=a.seed)
+    print("accuracy: ", m["accuracy_cm"])
+    print("completion: ", m["completion_cm"])
+    print("completion ratio: ", m["completion_ratio_pct"])
+
+
+if __name__ == "__main__":
+    main()
