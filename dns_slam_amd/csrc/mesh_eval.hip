@@ -1,4 +1,5 @@
-// Mesh evaluation (the reference's eval_3d.py / cull_mesh.py): nearest reference point of every query, and the frustum test.
+// Mesh evaluation (the reference's eval_3d.py / cull_mesh.py): nearest reference point of every query, the ICP alignment built
+// on it (dns_icp_point_to_point, described at its kernels below), and the frustum test.
 //
 // dns_nearest_points: for each query the Euclidean distance to the nearest of M reference points and that point's index
 // (cKDTree(ref).query(query) of eval_3d.py:24-42), over a uniform cell grid of the reference cloud:
@@ -312,13 +313,14 @@ __device__ __forceinline__ uint64_t nn_range(const float4* __restrict__ sorted, 
   return best;
 }
 
-__global__ __launch_bounds__(NN_BLOCK) void nn_query_kernel(NnWs w, uint32_t M, const float* __restrict__ query, uint32_t N,
-                                                            uint32_t max_ring, float* __restrict__ dist, int32_t* __restrict__ idx,
-                                                            uint32_t* __restrict__ status) {
-  const uint32_t q = blockIdx.x * NN_BLOCK + threadIdx.x;
-  if (q >= N) return;
+// The ring search of one query qv: -> true with the packed minimum in `best` once it is decided, false after max_ring rings.
+// BOUNDED (the ICP correspondence search): the search is also over -- with whatever candidate it holds, none of them within the
+// radius -- once the lower bound of every unseen point exceeds the radius (lb^2 > stop_d2, stop_d2 at or above every d2 the
+// correspondence rule accepts).
+template <bool BOUNDED>
+__device__ __forceinline__ bool nn_search(const NnWs& w, uint32_t M, const float (&qv)[3], uint32_t max_ring, float stop_d2,
+                                          uint64_t& best) {
   const NnHeader* h = w.head;
-  const float qv[3] = {query[3 * (size_t)q], query[3 * (size_t)q + 1], query[3 * (size_t)q + 2]};
   float t[3], slack[3], cellw[3];
   int c[3], dim[3];
 #pragma unroll
@@ -329,8 +331,6 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_query_kernel(NnWs w, uint32_t M, 
   }
   const uint32_t* __restrict__ start = w.start;
   const float4* __restrict__ sorted = w.sorted;
-  uint64_t best = NN_NONE;
-  bool done = false;
   for (uint32_t ring = 0; ring <= max_ring; ++ring) {
     const int r = (int)ring;
     const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, dim[0] - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, dim[1] - 1);
@@ -352,12 +352,20 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_query_kernel(NnWs w, uint32_t M, 
       if (up <= dim[d] - 1) lb = fminf(lb, fmaxf(((float)up - t[d]) - slack[d], 0.f) * cellw[d]);
       if (dn >= 1) lb = fminf(lb, fmaxf((t[d] - (float)dn) - slack[d], 0.f) * cellw[d]);
     }
-    if (__uint_as_float((uint32_t)(best >> 32)) <= lb * lb) {      // lb = inf: every cell has been seen
-      done = true;
-      break;
-    }
+    if (__uint_as_float((uint32_t)(best >> 32)) <= lb * lb) return true;      // lb = inf: every cell has been seen
+    if (BOUNDED && lb * lb > stop_d2) return true;
   }
-  if (done) {
+  return false;
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void nn_query_kernel(NnWs w, uint32_t M, const float* __restrict__ query, uint32_t N,
+                                                            uint32_t max_ring, float* __restrict__ dist, int32_t* __restrict__ idx,
+                                                            uint32_t* __restrict__ status) {
+  const uint32_t q = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (q >= N) return;
+  const float qv[3] = {query[3 * (size_t)q], query[3 * (size_t)q + 1], query[3 * (size_t)q + 2]};
+  uint64_t best = NN_NONE;
+  if (nn_search<false>(w, M, qv, max_ring, 0.f, best)) {
     dist[q] = sqrtf(__uint_as_float((uint32_t)(best >> 32)));
     idx[q] = (int32_t)(uint32_t)best;
   } else {
@@ -403,6 +411,235 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_finish_kernel(NnWs w, uint32_t N,
   const uint64_t best = w.best[q];
   dist[q] = sqrtf(__uint_as_float((uint32_t)(best >> 32)));
   idx[q] = (int32_t)(uint32_t)best;
+}
+
+// ---- point-to-point ICP (get_align_transformation of eval_3d.py:45-59) ---------------------------------------------------------
+// dns_icp_point_to_point: the grid over the target cloud built once, then max_iter + 1 passes of four launches:
+//   icp_query:  thread = source point.  p' = fl32(T p) from the float64 T in the workspace (kept in xf for the kernels after it),
+//               the ring search of nn_query bounded by the radius; the packed minimum of EVERY point goes to best[], the
+//               undecided ones to the todo list.
+//   nn_brute:   the all-pairs finish of the todo list, as in dns_nearest_points.
+//   icp_reduce: thread = source point (grid-stride over at most ICP_ROWS workgroups).  The correspondence rule, the 17 float64
+//               sums in registers, a butterfly over the wave, the waves through LDS in order, one row per workgroup.
+//   icp_solve:  one workgroup adds the rows in a fixed order; one thread applies the stopping rule or computes the rigid update
+//               (Horn's quaternion: the eigenvector of the largest eigenvalue of a symmetric 4x4, cyclic Jacobi) and composes it.
+// No floating-point atomics anywhere: the result is the same bits for every call.  After the stop `done` is set and every kernel
+// of the remaining passes returns at once (the all-pairs kernel over an empty todo list).
+constexpr uint32_t ICP_ROWS = 1024;                              // partial rows (workgroups of icp_reduce) at the most
+constexpr int ICP_SUMS = 17;                                     // n, sum p' (3), sum q (3), sum q p'^T (9), sum |p' - q|^2
+constexpr int ICP_RESULT = 21 + ICP_SUMS;                        // doubles of `result` (include/dns_hip.h)
+
+struct IcpInit {
+  double m[16];
+};
+
+struct IcpState {
+  double T[16];
+  double prev_fit, prev_rmse;
+  uint32_t qst[4];                                               // qst[1]: the todo count of the pass (the status words nn_brute reads)
+  uint32_t done, updates, pad[2];
+};
+
+__global__ void icp_begin_kernel(IcpState* __restrict__ s, IcpInit init, uint32_t* __restrict__ status, double* __restrict__ result) {
+  if (threadIdx.x || blockIdx.x) return;
+  for (int k = 0; k < 16; ++k) s->T[k] = init.m[k], result[k] = init.m[k];
+  for (int k = 16; k < ICP_RESULT; ++k) result[k] = 0.0;
+  s->prev_fit = 0.0, s->prev_rmse = 0.0;
+  for (int k = 0; k < 4; ++k) s->qst[k] = 0u;
+  s->updates = 0u;
+  const bool bad = status[0] != 0u;                              // a non-finite coordinate: nothing is evaluated
+  s->done = bad ? 1u : 0u;
+  status[3] = bad ? DNS_ICP_STOP_NONFINITE : DNS_ICP_STOP_MAX_ITER;
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void icp_query_kernel(NnWs w, uint32_t M, const float* __restrict__ src, uint32_t N,
+                                                             uint32_t max_ring, float stop_d2, IcpState* __restrict__ s,
+                                                             float* __restrict__ xf) {
+  if (s->done) return;
+  const uint32_t q = blockIdx.x * NN_BLOCK + threadIdx.x;
+  if (q >= N) return;
+  const double* T = s->T;
+  const double x = (double)src[3 * (size_t)q], y = (double)src[3 * (size_t)q + 1], z = (double)src[3 * (size_t)q + 2];
+  float qv[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) qv[d] = (float)(((T[4 * d] * x + T[4 * d + 1] * y) + T[4 * d + 2] * z) + T[4 * d + 3]);
+  xf[3 * (size_t)q] = qv[0], xf[3 * (size_t)q + 1] = qv[1], xf[3 * (size_t)q + 2] = qv[2];
+  uint64_t best = NN_NONE;
+  const bool decided = nn_search<true>(w, M, qv, max_ring, stop_d2, best);
+  w.best[q] = best;
+  if (!decided) {
+    const uint32_t pos = atomicAdd(&s->qst[1], 1u);
+    if (pos < N) w.todo[pos] = q;
+  }
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void icp_reduce_kernel(NnWs w, const float* __restrict__ tgt, uint32_t M,
+                                                              const float* __restrict__ xf, uint32_t N, float max_dist,
+                                                              const IcpState* __restrict__ s, double* __restrict__ partial) {
+  __shared__ double s_w[NN_BLOCK / WAVE][ICP_SUMS];
+  if (s->done) return;
+  double a[ICP_SUMS];
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; ++k) a[k] = 0.0;
+  for (uint32_t i = blockIdx.x * NN_BLOCK + threadIdx.x; i < N; i += gridDim.x * NN_BLOCK) {
+    const uint64_t best = w.best[i];
+    const uint32_t j = (uint32_t)best;
+    const float d = sqrtf(__uint_as_float((uint32_t)(best >> 32)));
+    if (j < M && d <= max_dist) {                                // the correspondence rule (a NaN distance fails it)
+      const double p[3] = {(double)xf[3 * (size_t)i], (double)xf[3 * (size_t)i + 1], (double)xf[3 * (size_t)i + 2]};
+      const double g[3] = {(double)tgt[3 * (size_t)j], (double)tgt[3 * (size_t)j + 1], (double)tgt[3 * (size_t)j + 2]};
+      a[0] += 1.0;
+      double d2 = 0.0;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        a[1 + r] += p[r], a[4 + r] += g[r];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a[7 + 3 * r + c] += g[r] * p[c];
+        const double e = p[r] - g[r];
+        d2 += e * e;
+      }
+      a[16] += d2;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; ++k)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o);
+  if (threadIdx.x % WAVE == 0)
+#pragma unroll
+    for (int k = 0; k < ICP_SUMS; ++k) s_w[threadIdx.x / WAVE][k] = a[k];
+  __syncthreads();
+  if (threadIdx.x < ICP_SUMS) {
+    double v = s_w[0][threadIdx.x];
+    for (int k = 1; k < NN_BLOCK / WAVE; ++k) v += s_w[k][threadIdx.x];
+    partial[(size_t)blockIdx.x * ICP_SUMS + threadIdx.x] = v;
+  }
+}
+
+// The eigenvector of the largest eigenvalue of the symmetric 4x4 A (cyclic Jacobi, float64); the first of equal eigenvalues.
+__device__ void icp_top_eigenvector(double A[4][4], double q[4]) {
+  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+  for (int sweep = 0; sweep < 50; ++sweep) {
+    double off = 0.0, all = 0.0;
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) {
+        all += A[i][j] * A[i][j];
+        if (i != j) off += A[i][j] * A[i][j];
+      }
+    if (!(off > 1e-30 * all)) break;                          // off-diagonal entries under 1e-15 of the matrix
+    for (int p = 0; p < 3; ++p)
+      for (int r = p + 1; r < 4; ++r) {
+        if (A[p][r] == 0.0) continue;
+        const double theta = (A[r][r] - A[p][p]) / (2.0 * A[p][r]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < 4; ++k) {                            // A <- A J
+          const double akp = A[k][p], akr = A[k][r];
+          A[k][p] = c * akp - sn * akr, A[k][r] = sn * akp + c * akr;
+        }
+        for (int k = 0; k < 4; ++k) {                            // A <- J^T A
+          const double apk = A[p][k], ark = A[r][k];
+          A[p][k] = c * apk - sn * ark, A[r][k] = sn * apk + c * ark;
+        }
+        for (int k = 0; k < 4; ++k) {
+          const double vkp = V[k][p], vkr = V[k][r];
+          V[k][p] = c * vkp - sn * vkr, V[k][r] = sn * vkp + c * vkr;
+        }
+      }
+  }
+  int top = 0;
+  for (int k = 1; k < 4; ++k)
+    if (A[k][k] > A[top][top]) top = k;
+  double nrm = 0.0;
+  for (int k = 0; k < 4; ++k) nrm += V[k][top] * V[k][top];
+  nrm = sqrt(nrm);
+  for (int k = 0; k < 4; ++k) q[k] = nrm > 0.0 ? V[k][top] / nrm : (k == 0 ? 1.0 : 0.0);
+}
+
+__global__ __launch_bounds__(NN_BLOCK) void icp_solve_kernel(const double* __restrict__ partial, uint32_t n_rows, uint32_t N,
+                                                             uint32_t pass, uint32_t max_iter, double rel_fit, double rel_rmse,
+                                                             IcpState* __restrict__ s, double* __restrict__ result,
+                                                             uint32_t* __restrict__ status) {
+  __shared__ double s_w[NN_BLOCK / WAVE][ICP_SUMS];
+  if (s->done) return;
+  double a[ICP_SUMS];
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; ++k) {
+    a[k] = 0.0;
+    for (uint32_t r = threadIdx.x; r < n_rows; r += NN_BLOCK) a[k] += partial[(size_t)r * ICP_SUMS + k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o);
+  }
+  if (threadIdx.x % WAVE == 0)
+#pragma unroll
+    for (int k = 0; k < ICP_SUMS; ++k) s_w[threadIdx.x / WAVE][k] = a[k];
+  __syncthreads();
+  if (threadIdx.x) return;
+  double sum[ICP_SUMS];
+  for (int k = 0; k < ICP_SUMS; ++k) {
+    sum[k] = s_w[0][k];
+    for (int v = 1; v < NN_BLOCK / WAVE; ++v) sum[k] += s_w[v][k];
+  }
+  const double n = sum[0];
+  const double fitness = n / (double)N, rmse = n > 0.0 ? sqrt(sum[16] / n) : 0.0;
+  status[1] += s->qst[1];
+  s->qst[1] = 0u;
+  uint32_t stop = 0xffffffffu;                                   // none
+  if (pass > 0 && fabs(fitness - s->prev_fit) < rel_fit && fabs(rmse - s->prev_rmse) < rel_rmse)
+    stop = DNS_ICP_STOP_CONVERGED;
+  else if (pass == max_iter)
+    stop = DNS_ICP_STOP_MAX_ITER;
+  else if (n < 3.0)
+    stop = DNS_ICP_STOP_FEW;
+  s->prev_fit = fitness, s->prev_rmse = rmse;
+  if (stop == 0xffffffffu) {
+    // M[i][j] = sum (p'_i - mean p'_i)(q_j - mean q_j) / n; Horn's N from it; R rotates the p' onto the q
+    double Mx[3][3], mp[3], mq[3];
+    for (int i = 0; i < 3; ++i) mp[i] = sum[1 + i] / n, mq[i] = sum[4 + i] / n;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) Mx[i][j] = sum[7 + 3 * j + i] / n - mp[i] * mq[j];
+    double A[4][4] = {
+        {Mx[0][0] + Mx[1][1] + Mx[2][2], Mx[1][2] - Mx[2][1], Mx[2][0] - Mx[0][2], Mx[0][1] - Mx[1][0]},
+        {Mx[1][2] - Mx[2][1], Mx[0][0] - Mx[1][1] - Mx[2][2], Mx[0][1] + Mx[1][0], Mx[2][0] + Mx[0][2]},
+        {Mx[2][0] - Mx[0][2], Mx[0][1] + Mx[1][0], -Mx[0][0] + Mx[1][1] - Mx[2][2], Mx[1][2] + Mx[2][1]},
+        {Mx[0][1] - Mx[1][0], Mx[2][0] + Mx[0][2], Mx[1][2] + Mx[2][1], -Mx[0][0] - Mx[1][1] + Mx[2][2]}};
+    double qt[4];
+    icp_top_eigenvector(A, qt);
+    const double qw = qt[0], qx = qt[1], qy = qt[2], qz = qt[3];
+    const double R[3][3] = {{1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qw * qz), 2.0 * (qx * qz + qw * qy)},
+                            {2.0 * (qx * qy + qw * qz), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qw * qx)},
+                            {2.0 * (qx * qz - qw * qy), 2.0 * (qy * qz + qw * qx), 1.0 - 2.0 * (qx * qx + qy * qy)}};
+    double U[3][4], Tn[3][4];
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) U[i][j] = R[i][j];
+      U[i][3] = mq[i] - (R[i][0] * mp[0] + R[i][1] * mp[1] + R[i][2] * mp[2]);
+    }
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 4; ++j)
+        Tn[i][j] = U[i][0] * s->T[j] + U[i][1] * s->T[4 + j] + U[i][2] * s->T[8 + j] + (j == 3 ? U[i][3] : 0.0);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 4; ++j) s->T[4 * i + j] = Tn[i][j];
+    s->updates += 1u;
+  } else {
+    s->done = 1u;
+    status[3] = stop;
+  }
+  for (int k = 0; k < 16; ++k) result[k] = s->T[k];
+  result[16] = fitness, result[17] = rmse, result[18] = n, result[19] = (double)s->updates;
+  result[20] = stop == DNS_ICP_STOP_CONVERGED ? 1.0 : 0.0;
+  for (int k = 0; k < ICP_SUMS; ++k) result[21 + k] = sum[k];
+}
+
+size_t icp_layout(void* ws, uint32_t M, uint32_t N, NnWs* w, IcpState** state, float** xf, double** partial) {
+  size_t off = nn_layout(ws, M, N, w);
+  char* p = (char*)ws;
+  if (state) *state = (IcpState*)(p + off);
+  off += align256(sizeof(IcpState));
+  if (xf) *xf = (float*)(p + off);
+  off += align256((size_t)N * 12);
+  if (partial) *partial = (double*)(p + off);
+  off += align256((size_t)ICP_ROWS * ICP_SUMS * 8);
+  return off;
 }
 
 // ---- frustum test --------------------------------------------------------------------------------------------------------
@@ -454,6 +691,38 @@ extern "C" uint64_t dns_nearest_ws_bytes(uint32_t M, uint32_t N) {
   return nn_layout(nullptr, M, N, nullptr);
 }
 
+namespace {
+
+inline dim3 nn_blocks(uint64_t n) { return dim3((uint32_t)((n + NN_BLOCK - 1) / NN_BLOCK)); }
+
+// cleared counters and status, the box of ref and the non-finite flags of both clouds
+void nn_launch_box(const NnWs& w, bool grid, const float* ref, uint32_t M, const float* query, uint32_t N, uint32_t* status,
+                   hipStream_t st) {
+  DNS_LAUNCH(nn_init_kernel, nn_blocks(grid ? (uint64_t)w.cells_alloc + 1 : 4), dim3(NN_BLOCK), 0, st, w, grid, status);
+  const uint32_t box_grid = (uint32_t)std::min<uint64_t>(NN_BOX_GRID, ((uint64_t)std::max(M, N) + NN_BOX_BLOCK - 1) / NN_BOX_BLOCK);
+  DNS_LAUNCH(nn_box_kernel, dim3(box_grid), dim3(NN_BOX_BLOCK), 0, st, ref, M, query, N, w.head, status);
+}
+
+// the build half: the cell grid over ref (after nn_launch_box), queried any number of times
+void nn_launch_build(const NnWs& w, const float* ref, uint32_t M, uint32_t* status, hipStream_t st) {
+  const uint32_t n_scan = w.cells_alloc / NN_SCAN_TILE;          // <= 1024
+  DNS_LAUNCH(nn_header_kernel, dim3(1), dim3(1), 0, st, w.head, w.target, status);
+  DNS_LAUNCH(nn_count_kernel, nn_blocks(M), dim3(NN_BLOCK), 0, st, ref, M, w);
+  DNS_LAUNCH(nn_scan_sums_kernel, dim3(n_scan), dim3(NN_BLOCK), 0, st, w);
+  DNS_LAUNCH(nn_scan_top_kernel, dim3(1), dim3(NN_SUMS_BLOCK), 0, st, w, n_scan);
+  DNS_LAUNCH(nn_scan_local_kernel, dim3(n_scan), dim3(NN_BLOCK), 0, st, w, M);
+  DNS_LAUNCH(nn_fill_kernel, nn_blocks(M), dim3(NN_BLOCK), 0, st, ref, M, w);
+}
+
+// the all-pairs finish of the todo list (count in status[1]) over w.sorted
+void nn_launch_brute(const NnWs& w, uint32_t M, const float* query, uint32_t N, const uint32_t* status, hipStream_t st) {
+  const uint32_t chunks = (M + NN_BRUTE_CHUNK - 1) / NN_BRUTE_CHUNK;
+  const uint32_t tiles = std::min(NN_BRUTE_GRID_Y, (N + NN_BLOCK - 1) / NN_BLOCK);
+  DNS_LAUNCH(nn_brute_kernel, dim3(chunks, tiles), dim3(NN_BLOCK), 0, st, w, M, query, N, status);
+}
+
+}  // namespace
+
 extern "C" int dns_nearest_points(const float* ref, uint32_t M, const float* query, uint32_t N, uint32_t max_ring, uint32_t flags,
                                   void* ws, float* dist, int32_t* idx, uint32_t* status, void* stream) {
   DNS_REQUIRE(M < (1u << 31) && N < (1u << 31), "dns_nearest_points: %u reference points, %u queries (must be < 2^31)", M, N);
@@ -466,27 +735,61 @@ extern "C" int dns_nearest_points(const float* ref, uint32_t M, const float* que
   NnWs w;
   nn_layout(ws, M, N, &w);
   const bool grid = !(flags & DNS_NEAREST_BRUTE);
-  const auto blocks = [](uint64_t n) { return dim3((uint32_t)((n + NN_BLOCK - 1) / NN_BLOCK)); };
-  DNS_LAUNCH(nn_init_kernel, blocks(grid ? (uint64_t)w.cells_alloc + 1 : 4), dim3(NN_BLOCK), 0, st, w, grid, status);
-  const uint32_t box_grid = (uint32_t)std::min<uint64_t>(NN_BOX_GRID, ((uint64_t)std::max(M, N) + NN_BOX_BLOCK - 1) / NN_BOX_BLOCK);
-  DNS_LAUNCH(nn_box_kernel, dim3(box_grid), dim3(NN_BOX_BLOCK), 0, st, ref, M, query, N, w.head, status);
+  nn_launch_box(w, grid, ref, M, query, N, status, st);
   if (grid) {
-    const uint32_t n_scan = w.cells_alloc / NN_SCAN_TILE;          // <= 1024
-    DNS_LAUNCH(nn_header_kernel, dim3(1), dim3(1), 0, st, w.head, w.target, status);
-    DNS_LAUNCH(nn_count_kernel, blocks(M), dim3(NN_BLOCK), 0, st, ref, M, w);
-    DNS_LAUNCH(nn_scan_sums_kernel, dim3(n_scan), dim3(NN_BLOCK), 0, st, w);
-    DNS_LAUNCH(nn_scan_top_kernel, dim3(1), dim3(NN_SUMS_BLOCK), 0, st, w, n_scan);
-    DNS_LAUNCH(nn_scan_local_kernel, dim3(n_scan), dim3(NN_BLOCK), 0, st, w, M);
-    DNS_LAUNCH(nn_fill_kernel, blocks(M), dim3(NN_BLOCK), 0, st, ref, M, w);
-    DNS_LAUNCH(nn_query_kernel, blocks(N), dim3(NN_BLOCK), 0, st, w, M, query, N, max_ring, dist, idx, status);
+    nn_launch_build(w, ref, M, status, st);
+    DNS_LAUNCH(nn_query_kernel, nn_blocks(N), dim3(NN_BLOCK), 0, st, w, M, query, N, max_ring, dist, idx, status);
   } else {
-    DNS_LAUNCH(nn_pack_kernel, blocks(std::max(M, N)), dim3(NN_BLOCK), 0, st, ref, M, N, w, status);
+    DNS_LAUNCH(nn_pack_kernel, nn_blocks(std::max(M, N)), dim3(NN_BLOCK), 0, st, ref, M, N, w, status);
   }
-  const uint32_t chunks = (M + NN_BRUTE_CHUNK - 1) / NN_BRUTE_CHUNK;
-  const uint32_t tiles = std::min(NN_BRUTE_GRID_Y, (N + NN_BLOCK - 1) / NN_BLOCK);
-  DNS_LAUNCH(nn_brute_kernel, dim3(chunks, tiles), dim3(NN_BLOCK), 0, st, w, M, query, N, (const uint32_t*)status);
-  DNS_LAUNCH(nn_finish_kernel, blocks(N), dim3(NN_BLOCK), 0, st, w, N, dist, idx, (const uint32_t*)status);
+  nn_launch_brute(w, M, query, N, (const uint32_t*)status, st);
+  DNS_LAUNCH(nn_finish_kernel, nn_blocks(N), dim3(NN_BLOCK), 0, st, w, N, dist, idx, (const uint32_t*)status);
   return check_launch("dns_nearest_points");
+}
+
+extern "C" uint64_t dns_icp_ws_bytes(uint32_t M, uint32_t N) {
+  if (M >= (1u << 31) || N >= (1u << 31) || M == 0 || N == 0) return 0;
+  return icp_layout(nullptr, M, N, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int dns_icp_point_to_point(const float* src, uint32_t N, const float* tgt, uint32_t M, const double* init, float max_dist,
+                                      uint32_t max_iter, double rel_fitness, double rel_rmse, uint32_t max_ring, void* ws,
+                                      double* result, uint32_t* status, void* stream) {
+  DNS_REQUIRE(M > 0 && N > 0, "dns_icp_point_to_point: %u source points, %u target points (an empty cloud)", N, M);
+  DNS_REQUIRE(M < (1u << 31) && N < (1u << 31), "dns_icp_point_to_point: %u source points, %u target points (must be < 2^31)", N, M);
+  DNS_REQUIRE(max_ring <= 64u, "dns_icp_point_to_point: max_ring %u (must be <= 64)", max_ring);
+  DNS_REQUIRE(max_iter <= DNS_ICP_MAX_ITER, "dns_icp_point_to_point: max_iter %u (must be <= %u)", max_iter, DNS_ICP_MAX_ITER);
+  DNS_REQUIRE(max_dist > 0.f && max_dist <= 3.0e38f, "dns_icp_point_to_point: max_dist %g (must be positive and finite)",
+              (double)max_dist);
+  DNS_REQUIRE(rel_fitness >= 0.0 && rel_rmse >= 0.0, "dns_icp_point_to_point: negative (or NaN) relative_fitness / relative_rmse");
+  DNS_REQUIRE(src && tgt && ws && result && status, "dns_icp_point_to_point: NULL argument");
+  IcpInit t0;
+  for (int k = 0; k < 16; ++k) {
+    t0.m[k] = init ? init[k] : (k % 5 == 0 ? 1.0 : 0.0);
+    DNS_REQUIRE(t0.m[k] - t0.m[k] == 0.0, "dns_icp_point_to_point: init[%d] is not finite", k);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  NnWs w;
+  IcpState* state;
+  float* xf;
+  double* partial;
+  icp_layout(ws, M, N, &w, &state, &xf, &partial);
+  // at or above every d2 whose fp32 root is <= max_dist (2^-21 covers the rounding of the square and of the root)
+  const double md2 = (double)max_dist * (double)max_dist * (1.0 + 0x1p-21);
+  const float stop_d2 = md2 < 3.0e38 ? (float)md2 : __builtin_inff();
+  const uint32_t rows = std::min(ICP_ROWS, (N + NN_BLOCK - 1) / NN_BLOCK);
+  nn_launch_box(w, true, tgt, M, src, N, status, st);
+  nn_launch_build(w, tgt, M, status, st);
+  DNS_LAUNCH(icp_begin_kernel, dim3(1), dim3(1), 0, st, state, t0, status, result);
+  for (uint32_t pass = 0; pass <= max_iter; ++pass) {
+    DNS_LAUNCH(icp_query_kernel, nn_blocks(N), dim3(NN_BLOCK), 0, st, w, M, src, N, max_ring, stop_d2, state, xf);
+    nn_launch_brute(w, M, xf, N, (const uint32_t*)state->qst, st);
+    DNS_LAUNCH(icp_reduce_kernel, dim3(rows), dim3(NN_BLOCK), 0, st, w, tgt, M, (const float*)xf, N, max_dist,
+               (const IcpState*)state, partial);
+    DNS_LAUNCH(icp_solve_kernel, dim3(1), dim3(NN_BLOCK), 0, st, (const double*)partial, rows, N, pass, max_iter, rel_fitness,
+               rel_rmse, state, result, status);
+  }
+  return check_launch("dns_icp_point_to_point");
 }
 
 extern "C" int dns_frustum_seen(const float* pts, uint32_t P, const float* w2c, uint32_t K, int H, int W, const float* intr,

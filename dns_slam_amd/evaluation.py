@@ -3,7 +3,9 @@
 ``read_ply`` / ``load_poses`` read what the tools take from disk; ``cull_mesh`` drops the faces no camera of a trajectory sees
 (``ops.frustum_seen``); ``sample_surface`` is trimesh's area-weighted surface sampler; ``accuracy`` / ``completion`` /
 ``completion_ratio`` are the nearest-neighbour metrics (``ops.nearest_points`` in place of the host KD-tree) and ``metrics_3d``
-the three of them for two meshes.  The ICP alignment of the reference (open3d) is not implemented.
+the three of them for two meshes.  ``align_transformation`` is the reference's ICP alignment (open3d's point-to-point
+``registration_icp``, restated by ``ops.icp_point_to_point``) and ``calc_3d_metric`` the reference's function under its own name:
+the alignment, then ``metrics_3d``.
 """
 from __future__ import annotations
 
@@ -215,10 +217,10 @@ def metrics_3d(rec_verts, rec_faces, gt_verts, gt_faces, n_samples=200000, dist_
     """calc_3d_metric (eval_3d.py:91-117) -> {"accuracy_cm", "completion_cm", "completion_ratio_pct"}: ``n_samples`` points on
     each mesh (the reconstruction first, from one device generator seeded with ``seed``; or the uniforms ``u_rec`` / ``u_gt``),
     two nearest-point passes, the means in float64 on the device.  One host read at the end carries the three figures and every
-    error flag.  ``align=True`` (the reference's open3d ICP, its default) is not implemented."""
+    error flag.  ``align=True`` is refused: ``calc_3d_metric`` aligns (the reference's default) and then calls this."""
     if align:
-        raise NotImplementedError("metrics_3d: align=True (get_align_transformation, open3d's point-to-point ICP) is not "
-                                  "implemented; align the meshes beforehand")
+        raise NotImplementedError("metrics_3d: align=True is not implemented here; calc_3d_metric aligns the meshes "
+                                  "(align_transformation, the reference's point-to-point ICP) and then measures")
     dev = rec_verts.device
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
@@ -234,3 +236,39 @@ def metrics_3d(rec_verts, rec_faces, gt_verts, gt_faces, n_samples=200000, dist_
     if out[5] or out[6]:
         raise ValueError("metrics_3d: non-finite coordinate in a mesh")
     return {"accuracy_cm": out[0], "completion_cm": out[1], "completion_ratio_pct": out[2]}
+
+
+def align_transformation(rec_verts, gt_verts, threshold=0.1, return_info=False):
+    """get_align_transformation (eval_3d.py:45-59): the rigid motion that registers the reconstruction's vertices rec_verts
+    [V,3] to the ground truth's gt_verts [W,3] by point-to-point ICP from the identity, correspondence distance ``threshold``,
+    open3d's default criteria (30 iterations, relative fitness and rmse 1e-6) -> float64 [4,4] on the device; with
+    ``return_info`` also the dict of ``ops.icp_point_to_point``."""
+    info = ops.icp_point_to_point(rec_verts, gt_verts, max_dist=threshold)
+    return (info["transformation"], info) if return_info else info["transformation"]
+
+
+def apply_transform(verts, T):
+    """mesh.apply_transform(T) for the vertices: verts [V,3] -> fp32 [V,3] = R v + t, computed in float64 and rounded once."""
+    T = torch.as_tensor(T, dtype=torch.float64).to(verts.device)
+    if T.shape != (4, 4):
+        raise ValueError(f"apply_transform: T must be [4,4], got {tuple(T.shape)}")
+    return (verts.detach().double() @ T[:3, :3].T + T[:3, 3]).float()
+
+
+def calc_3d_metric(rec_verts, rec_faces, gt_verts, gt_faces, align=True, threshold=0.1, n_samples=200000, dist_th=0.05, seed=0,
+                   u_rec=None, u_gt=None):
+    """calc_3d_metric (eval_3d.py:91-117) with the reference's default: with ``align`` the reconstruction's vertices are first
+    registered to the ground truth's (``align_transformation``) and moved (``apply_transform``); then ``metrics_3d`` -> its dict
+    plus "transformation" (float64 [4,4] on the device; the identity without ``align``) and, with ``align``, "icp" (fitness,
+    inlier_rmse, iterations, converged of the registration)."""
+    if align:
+        T, info = align_transformation(rec_verts, gt_verts, threshold, return_info=True)
+        rec_verts = apply_transform(rec_verts, T)
+    else:
+        T, info = torch.eye(4, dtype=torch.float64, device=rec_verts.device), None
+    out = metrics_3d(rec_verts, rec_faces, gt_verts, gt_faces, n_samples=n_samples, dist_th=dist_th, seed=seed, align=False,
+                     u_rec=u_rec, u_gt=u_gt)
+    out["transformation"] = T
+    if info is not None:
+        out["icp"] = {k: info[k] for k in ("fitness", "inlier_rmse", "correspondences", "iterations", "converged")}
+    return out

@@ -6,6 +6,7 @@ happens in libdns_hip.so; nothing in this module has a CPU or eager-torch fallba
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import os
@@ -1038,6 +1039,75 @@ def nearest_points(ref: torch.Tensor, query: torch.Tensor, method: str = "grid",
         raise ValueError("nearest_points: non-finite coordinate in " + " and ".join(
             n for b, n in ((1, "ref"), (2, "query")) if bad & b))
     return (dist, idx, {"brute_queries": n_brute, "cells": cells}) if return_stats else (dist, idx)
+
+
+ICP_STOP_REASONS = ("max_iter", "converged", "few_correspondences", "non_finite")     # status[3] of dns_icp_point_to_point
+
+
+def _icp_arguments(source, target, max_dist, init, max_iter, relative_fitness, relative_rmse):
+    s = source.detach().contiguous().float() if isinstance(source, torch.Tensor) else source
+    t = target.detach().contiguous().float() if isinstance(target, torch.Tensor) else target
+    require_cuda(s, t)
+    if s.dim() != 2 or s.shape[1] != 3 or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"icp_point_to_point: source [N,3] and target [M,3], got {tuple(s.shape)} and {tuple(t.shape)}")
+    if s.shape[0] == 0 or t.shape[0] == 0:
+        raise ValueError(f"icp_point_to_point: an empty cloud ({s.shape[0]} source points, {t.shape[0]} target points)")
+    md = float(max_dist)
+    if not (md > 0.0 and math.isfinite(md)):
+        raise ValueError(f"icp_point_to_point: max_dist must be positive and finite, got {max_dist!r}")
+    if int(max_iter) < 0:
+        raise ValueError(f"icp_point_to_point: max_iter {max_iter}")
+    if not (float(relative_fitness) >= 0.0 and float(relative_rmse) >= 0.0):
+        raise ValueError("icp_point_to_point: relative_fitness and relative_rmse must be >= 0")
+    t0 = None
+    if init is not None:
+        m = init.detach().cpu() if isinstance(init, torch.Tensor) else torch.as_tensor(init)
+        m = m.to(torch.float64)
+        if m.shape != (4, 4) or not bool(torch.isfinite(m).all()):
+            raise ValueError("icp_point_to_point: init must be a finite [4,4] matrix")
+        t0 = (C.c_double * 16)(*m.reshape(-1).tolist())
+    return s, t, md, t0
+
+
+def icp_point_to_point_launch(source: torch.Tensor, target: torch.Tensor, max_dist: float = 0.1, init=None, max_iter: int = 30,
+                              relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, max_rings: int = NEAREST_MAX_RINGS):
+    """``icp_point_to_point`` without its host read: -> (result [38] float64, status [4] int32, both on the device; the layout
+    of include/dns_hip.h).  ``init`` is a host matrix (a device tensor is read back: pass a host one to keep this free of
+    host reads)."""
+    s, t, md, t0 = _icp_arguments(source, target, max_dist, init, max_iter, relative_fitness, relative_rmse)
+    N, M = int(s.shape[0]), int(t.shape[0])
+    ws_b = int(_rawlib.dns_icp_ws_bytes(M, N))
+    if ws_b == 0:
+        raise ValueError(f"icp_point_to_point: {N} source / {M} target points are too many (>= 2^31)")
+    dev = s.device
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    result = torch.empty(38, dtype=torch.float64, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    check(lib.dns_icp_point_to_point(ptr(s), N, ptr(t), M, t0, md, int(max_iter), float(relative_fitness), float(relative_rmse),
+                                     int(max_rings), ptr(ws), ptr(result), ptr(status), stream_ptr()), "dns_icp_point_to_point")
+    return result, status
+
+
+def icp_point_to_point(source: torch.Tensor, target: torch.Tensor, max_dist: float = 0.1, init=None, max_iter: int = 30,
+                       relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, max_rings: int = NEAREST_MAX_RINGS):
+    """open3d's ``registration_icp(source, target, max_dist, init, TransformationEstimationPointToPoint(),
+    ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iter))`` (eval_3d.py:45-59) for source [N,3] and target [M,3]
+    fp32 on the device, as one launch sequence (include/dns_hip.h) -> {"transformation": float64 [4,4] on the device (source ->
+    target), "fitness", "inlier_rmse", "correspondences", "iterations" (updates applied), "converged", "stop" (one of
+    ICP_STOP_REASONS), "brute_queries", "sums" (float64 [17] on the host: n, sum p', sum q, sum q p'^T, sum |p' - q|^2 of the last
+    pass)}.  A correspondence is a nearest target point at a distance <= ``max_dist`` of the transformed source point.  CPU
+    tensors, wrong shapes, empty clouds, non-finite coordinates and ``max_dist`` <= 0 or not finite raise ValueError.  One host
+    read."""
+    result, status = icp_point_to_point_launch(source, target, max_dist, init, max_iter, relative_fitness, relative_rmse, max_rings)
+    host = torch.cat((result, status.double())).cpu()
+    bad, n_brute, _, stop = (int(x) for x in host[38:].tolist())
+    if bad:
+        raise ValueError("icp_point_to_point: non-finite coordinate in " + " and ".join(
+            n for b, n in ((1, "target"), (2, "source")) if bad & b))
+    r = host[:38].tolist()
+    return {"transformation": result[:16].view(4, 4), "fitness": r[16], "inlier_rmse": r[17], "correspondences": int(r[18]),
+            "iterations": int(r[19]), "converged": bool(r[20]), "stop": ICP_STOP_REASONS[stop], "brute_queries": n_brute,
+            "sums": host[21:38].numpy().copy()}
 
 
 def frustum_seen(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: float, fy: float, cx: float, cy: float):

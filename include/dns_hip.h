@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 15
+#define DNS_ABI_VERSION 16
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -652,7 +652,7 @@ uint64_t dns_mesh_cc_ws_bytes(uint32_t F);
 int dns_mesh_components(const float* verts, uint32_t V, const int32_t* faces, uint32_t F, void* ws, int32_t* comp, double* comp_area,
                         uint32_t* status, void* stream);
 
-/* ---- mesh evaluation (eval_3d.py, cull_mesh.py of the reference; csrc/mesh_eval.hip; ABI v15) ---------------------------
+/* ---- mesh evaluation (eval_3d.py, cull_mesh.py of the reference; csrc/mesh_eval.hip; ABI v15, v16) ---------------------------
  * dns_nearest_points: for each of N queries query [N,3] fp32 the Euclidean distance dist [N] fp32 to the nearest of M reference
  * points ref [M,3] fp32 and that point's index idx [N] int32 (cKDTree(ref).query(query), eval_3d.py:24-42).  Every pair
  * distance is sqrt of the fp32 sum dx dx + dy dy + dz dz (no contraction); among equal distances the smaller index wins, so
@@ -670,6 +670,46 @@ int dns_mesh_components(const float* verts, uint32_t V, const int32_t* faces, ui
 uint64_t dns_nearest_ws_bytes(uint32_t M, uint32_t N);
 int dns_nearest_points(const float* ref, uint32_t M, const float* query, uint32_t N, uint32_t max_ring, uint32_t flags, void* ws,
                        float* dist, int32_t* idx, uint32_t* status, void* stream);
+
+/* dns_icp_point_to_point (ABI v16): get_align_transformation of eval_3d.py:45-59 -- open3d's registration_icp with
+ * TransformationEstimationPointToPoint -- of the source cloud src [N,3] fp32 onto the target cloud tgt [M,3] fp32, as ONE fixed
+ * sequence of launches on the stream with no host read inside.  The cell grid of dns_nearest_points is built once over tgt; then
+ * max_iter + 1 passes, pass 0 evaluating init [host, 16 doubles, row-major 4x4; NULL = identity] and pass k the transformation
+ * after k updates.  A pass:
+ *   - p' = fl32(T p): ((T[i][0] x + T[i][1] y) + T[i][2] z) + T[i][3] in float64 from the float64 T held in the workspace, rounded
+ *     once to fp32; always from the ORIGINAL src (open3d transforms its float64 copy of the cloud update by update);
+ *   - the nearest target point of p' under the pair distance and tie rule of dns_nearest_points (the smaller index), by the same
+ *     ring search, which here also gives up once every unseen target point is provably farther than max_dist; the queries still
+ *     undecided after max_ring (<= 64) rings go through the all-pairs pass, so the answer is exact for every max_dist;
+ *   - a correspondence exists iff that fp32 distance is <= max_dist (inclusive; open3d's radius search is exclusive);
+ *   - the 17 sums n, sum p' [3], sum q [3], sum q p'^T [9, row = q], sum |p' - q|^2 in float64 from the fp32 coordinates: per
+ *     wave, per workgroup, one row per workgroup, the rows added by one workgroup in a fixed order.  No floating-point atomics:
+ *     `result` is the same bits for every call;
+ *   - fitness = n / N, inlier_rmse = sqrt(sum |p' - q|^2 / n) (0 without correspondences).  After pass k > 0 the registration stops
+ *     (converged) when |fitness - previous| < rel_fitness and |inlier_rmse - previous| < rel_rmse; it stops after pass max_iter;
+ *     otherwise T <- U T with U the rigid motion minimising sum |U p' - q|^2: the proper rotation maximising tr(R^T Sigma)
+ *     (Horn's quaternion form, the eigenvector of a symmetric 4x4 by cyclic Jacobi in float64) and t = mean q - R mean p'.
+ * After the stop the kernels of the remaining passes return at once.
+ *   dns_icp_ws_bytes: bytes of workspace (0: refused size -- an empty cloud, or M or N >= 2^31).
+ *   result [DNS_ICP_RESULT_DOUBLES] float64 (device): [0..16) T row-major, [16] fitness, [17] inlier_rmse, [18] n, [19] the number
+ *     of updates applied, [20] 1 if the stopping rule ended the registration, [21..38) the 17 sums of the last evaluated pass, which
+ *     is the pass that evaluated T.
+ *   status [4] uint32 (device): status[0] = the non-finite bits of dns_nearest_points (bit 0 tgt, bit 1 src); status[1] = the
+ *     queries the all-pairs pass finished, over all passes; status[2] = the number of grid cells; status[3] = why it stopped:
+ *     DNS_ICP_STOP_MAX_ITER, _CONVERGED, _FEW (fewer than 3 correspondences: no update is defined; T stays as it is) or
+ *     _NONFINITE (a non-finite coordinate in either cloud: nothing is evaluated, T = init, the other figures 0).
+ * An empty cloud, max_dist <= 0 or not finite, a non-finite init, negative criteria and max_iter > DNS_ICP_MAX_ITER are refused.
+ * Every store lies inside the sizes passed in, whatever the coordinates and init. */
+#define DNS_ICP_RESULT_DOUBLES 38
+#define DNS_ICP_MAX_ITER 1000u
+#define DNS_ICP_STOP_MAX_ITER 0u
+#define DNS_ICP_STOP_CONVERGED 1u
+#define DNS_ICP_STOP_FEW 2u
+#define DNS_ICP_STOP_NONFINITE 3u
+uint64_t dns_icp_ws_bytes(uint32_t M, uint32_t N);
+int dns_icp_point_to_point(const float* src, uint32_t N, const float* tgt, uint32_t M, const double* init, float max_dist,
+                           uint32_t max_iter, double rel_fitness, double rel_rmse, uint32_t max_ring, void* ws, double* result,
+                           uint32_t* status, void* stream);
 
 /* dns_frustum_seen: seen [P] uint8 = some of the K poses w2c [K,16] (row-major world->camera, fp32) sees the point pts [P,3]:
  * check_proj of eval_3d.py:62-88 and the loop of cull_mesh.py:53-74 in fp32: cam = w2c @ [p,1], x = -cam.x, z' = cam.z + 1e-5,

@@ -1,9 +1,13 @@
 """Accuracy (cm), completion (cm) and completion ratio (%) of a reconstructed mesh against a ground-truth mesh: the
-reference's eval_3d.py (calc_3d_metric without the ICP alignment), preceded by its cull_mesh.py when a trajectory is given.
+reference's eval_3d.py (calc_3d_metric), preceded by its cull_mesh.py when a trajectory is given.
 
-    python tools/eval_mesh.py --rec A.ply --gt B.ply [--traj T --H 680 --W 1200 --fx 600 --fy 600 --cx 599.5 --cy 339.5]
+    python tools/eval_mesh.py --rec A.ply --gt B.ply [--align [--align-threshold 0.1]]
+                              [--traj T --H 680 --W 1200 --fx 600 --fy 600 --cx 599.5 --cy 339.5]
                               [--n 200000] [--dist-th 0.05] [--seed 0]
 
+--align: register the vertices of --rec to those of --gt first (the reference's get_align_transformation: point-to-point ICP from
+    the identity, correspondence distance 0.1, its default in calc_3d_metric); the transformation, fitness and inlier rmse go to
+    stderr.  Off by default here: without it the meshes are measured as they are.
 --traj: text file of camera-to-world poses, 16 numbers per line; the faces of --rec no pose sees are dropped first.
 """
 import argparse
@@ -31,6 +35,8 @@ def main():
     ap.add_argument("--n", type=int, default=200000)
     ap.add_argument("--dist-th", type=float, default=0.05)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--align", action="store_true")
+    ap.add_argument("--align-threshold", type=float, default=0.1)
     a = ap.parse_args()
     dev = "cuda:0"
     rec, gt = E.read_ply(a.rec), E.read_ply(a.gt)
@@ -40,7 +46,14 @@ def main():
         n_faces = rf.shape[0]
         rv, rf = E.cull_mesh(rv, rf, E.load_poses(a.traj), a.H, a.W, a.fx, a.fy, a.cx, a.cy)
         print(f"culled {n_faces - rf.shape[0]} of {n_faces} faces", file=sys.stderr)
-    m = E.metrics_3d(rv, rf, gv, gf, n_samples=a.n, dist_th=a.dist_th, seed=a.seed)
+    m = E.calc_3d_metric(rv, rf, gv, gf, align=a.align, threshold=a.align_threshold, n_samples=a.n, dist_th=a.dist_th, seed=a.seed)
+    if a.align:
+        icp = m["icp"]
+        print("transformation:", file=sys.stderr)
+        for row in m["transformation"].cpu().tolist():
+            print("  " + " ".join(f"{x: .9f}" for x in row), file=sys.stderr)
+        print(f"fitness {icp['fitness']:.6f}, inlier rmse {icp['inlier_rmse']:.6f} ({icp['correspondences']} correspondences, "
+              f"{icp['iterations']} updates, {'converged' if icp['converged'] else 'not converged'})", file=sys.stderr)
     print("accuracy: ", m["accuracy_cm"])
     print("completion: ", m["completion_cm"])
     print("completion ratio: ", m["completion_ratio_pct"])
