@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class DnsGridMeta(C.Structure):
@@ -135,6 +135,10 @@ SIGNATURES = {
     "dns_icp_point_to_point": (C.c_int, [_P, _U, _P, _U, C.POINTER(C.c_double), C.c_float, _U, C.c_double, C.c_double, _U, _P, _P,
                                          _P, _P]),
     "dns_frustum_seen": (C.c_int, [_P, _U, _P, _U, _I, _I, C.POINTER(C.c_float), _P, _P]),
+    "dns_ms_ssim_window": (None, [C.POINTER(C.c_float)]),
+    "dns_ms_ssim_ws_bytes": (C.c_uint64, [_U, _U, _U]),
+    "dns_ms_ssim": (C.c_int, [_P, _P, _P, _U, _U, _U, _P, _P, _P, _P, _P, _P]),
+    "dns_label_confusion": (C.c_int, [_P, _P, _U, C.c_uint64, _U, _P, _P, _P]),
 }
 
 

@@ -6,6 +6,13 @@
 the three of them for two meshes.  ``align_transformation`` is the reference's ICP alignment (open3d's point-to-point
 ``registration_icp``, restated by ``ops.icp_point_to_point``) and ``calc_3d_metric`` the reference's function under its own name:
 the alignment, then ``metrics_3d``.
+
+2-D evaluation and trajectory error: the reference's ``eval_2d.py`` and ``eval_ate.py``.  ``psnr`` / ``ms_ssim`` score rendered
+images (``ops.ms_ssim``: MS-SSIM and the masked MSE in one launch sequence), ``semantic_metrics`` turns a confusion matrix
+(``ops.label_confusion``) into mIoU / fwIoU / accuracies, ``render_metrics`` is the loop of eval_2d.py:398-411 over a frame list
+with one host read at the end, and ``evaluate_ate`` the absolute trajectory error after the closed-form rigid alignment.  LPIPS is
+not computed: it needs AlexNet and the LPIPS linear-layer weights, which this repository does not ship; the result dict has no
+``lpips`` key.
 """
 from __future__ import annotations
 
@@ -272,3 +279,114 @@ def calc_3d_metric(rec_verts, rec_faces, gt_verts, gt_faces, align=True, thresho
     if info is not None:
         out["icp"] = {k: info[k] for k in ("fitness", "inlier_rmse", "correspondences", "iterations", "converged")}
     return out
+
+
+# ------------------------------------------------------------------------------------------- 2-D evaluation (eval_2d.py)
+def psnr(pred, gt, depth=None):
+    """eval_2d.py:299-301: -10 log10(mse) with the mse over the three channels of the pixels with ``depth`` > 0 (every pixel without
+    ``depth``).  pred, gt [H,W,3] or [F,H,W,3] on the device -> float64 device tensor (0-d or [F]); NaN where no pixel is valid."""
+    return -10.0 * torch.log10(ops.ms_ssim(pred, gt, depth)["mse"])
+
+
+def ms_ssim(pred, gt):
+    """eval_2d.py:302: pytorch_msssim's ms_ssim(data_range=1.0, size_average=True) per image pair (the reference passes the images
+    transposed to [1,3,W,H]; the definition is symmetric in the two axes) -> float64 device tensor (0-d or [F])."""
+    return ops.ms_ssim(pred, gt)["ms_ssim"]
+
+
+def semantic_metrics(conf, n_invalid=None) -> dict:
+    """eval_2d.py:180-213 from the confusion matrix conf [C,C] (rows = ground truth; ``ops.label_confusion``), on the host in
+    float64 -> {"miou", "fwiou", "class_avg_accuracy", "total_accuracy", "iou" [C] (NaN for classes in neither image)}.  The
+    reference's classes are the labels present in the ground truth: with row = conf.sum(1), col = conf.sum(0), present = row > 0,
+    iou_c = conf[c,c] / (row_c + col_c - conf[c,c]); miou = mean of iou over the present classes; fwiou = sum over them of
+    iou_c row_c / sum row; class_avg_accuracy = mean over them of conf[c,c] / (row_c + 1e-10); total_accuracy = trace / sum.
+    ``n_invalid`` != 0 (labels outside [0, C)) raises ValueError: the reference would treat each out-of-range value as one more
+    class (one more term in the means for a ground-truth value, misses for a predicted one), which a C x C matrix cannot hold."""
+    c = conf.detach().cpu().numpy() if isinstance(conf, torch.Tensor) else np.asarray(conf)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise ValueError(f"semantic_metrics: conf must be [C,C], got {c.shape}")
+    if n_invalid is not None and int(n_invalid) != 0:
+        raise ValueError(f"semantic_metrics: {int(n_invalid)} pixels hold a label outside [0, {c.shape[0]})")
+    c = c.astype(np.float64)
+    row, col, diag = c.sum(1), c.sum(0), np.diag(c)
+    total = row.sum()
+    if not total > 0:
+        raise ValueError("semantic_metrics: the confusion matrix is empty")
+    present = row > 0
+    union = row + col - diag
+    iou = np.full(c.shape[0], np.nan)
+    iou[union > 0] = diag[union > 0] / union[union > 0]
+    return {"miou": float(iou[present].mean()), "fwiou": float((iou[present] * row[present]).sum() / total),
+            "class_avg_accuracy": float((diag[present] / (row[present] + 1e-10)).mean()),
+            "total_accuracy": float(diag.sum() / total), "iou": iou}
+
+
+def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_batch=None, jitters=None) -> dict:
+    """The loop of eval_2d.py:398-411: for each chosen frame i (``indices``, or every ``every``-th frame) ``mapper.render_frame``
+    from ``frames["est_c2w"][i]``, then PSNR over the pixels with gt_depth > 0, MS-SSIM and the four semantic figures of the
+    arg-max label image against ``frames["gt_label"][i]`` (classes = the decoder's n_class).  The metric kernels are queued behind
+    each render; the host reads everything back once, after the last frame.  ``features`` / ``jitters``: per chosen frame, what
+    ``render_frame`` takes (None: no 2-D code / fresh draws).  -> {"frames": [i...], "psnr", "ssim", "miou", "fwiou",
+    "class_avg_accuracy", "total_accuracy": {"per_frame": float64 array, "mean": float}}; no "lpips" (see the module docstring)."""
+    n = int(frames["gt_color"].shape[0])
+    idx = list(range(0, n, int(every))) if indices is None else [int(i) for i in indices]
+    if not idx:
+        raise ValueError("render_metrics: no frames chosen")
+    for name, seq in (("features", features), ("jitters", jitters)):
+        if seq is not None and len(seq) != len(idx):
+            raise ValueError(f"render_metrics: {name} must hold one entry per chosen frame ({len(idx)}), got {len(seq)}")
+    dev = mapper.device
+    n_class = int(mapper.decoder.n_class)
+    vals, mses, confs, bads = [], [], [], []
+    for k, i in enumerate(idx):
+        gt_color, gt_depth, gt_label = frames["gt_color"][i], frames["gt_depth"][i], frames["gt_label"][i]
+        color, _, label = mapper.render_frame(gt_color, gt_depth, gt_label, frames["est_c2w"][i],
+                                              features=None if features is None else features[k], n_pts_batch=n_pts_batch,
+                                              jitter=None if jitters is None else jitters[k])
+        v, m, _, _ = ops.ms_ssim_launch(color, gt_color.to(dev), gt_depth.to(dev))
+        cf, bad = ops.label_confusion(gt_label.to(dev).reshape(label.shape), label, n_class)
+        vals.append(v), mses.append(m), confs.append(cf.reshape(-1)), bads.append(bad.reshape(1))
+    host = torch.cat((torch.cat(vals), torch.cat(mses), torch.cat(bads).double(), torch.cat(confs).double())).cpu().numpy()
+    F = len(idx)
+    ssim, mse, bad = host[:F], host[F:2 * F], host[2 * F:3 * F]
+    conf = host[3 * F:].reshape(F, n_class, n_class)
+    sem = [semantic_metrics(conf[k], bad[k]) for k in range(F)]
+    per = {"psnr": -10.0 * np.log10(mse), "ssim": ssim.copy()}
+    for key in ("miou", "fwiou", "class_avg_accuracy", "total_accuracy"):
+        per[key] = np.array([s[key] for s in sem], np.float64)
+    out = {key: {"per_frame": v, "mean": float(np.mean(v))} for key, v in per.items()}
+    out["frames"] = idx
+    return out
+
+
+# ------------------------------------------------------------------------------------------- trajectory error (eval_ate.py)
+def evaluate_ate(gt_c2w, est_c2w, scale=1.0) -> dict:
+    """eval_ate.py: the absolute trajectory error of the estimated camera centres against the ground truth's after the
+    closed-form rigid alignment (Horn / Kabsch), in numpy float64.  gt_c2w, est_c2w [K,4,4] (tensors or arrays).  Frames whose
+    ground-truth pose holds inf or NaN are dropped from both lists (convert_poses); translations are divided by ``scale``; with the
+    centred clouds e (estimate) and g, W = sum e g^T, U S V^T = svd(W^T), rot = U diag(1, 1, det(U) det(V^T)) V^T, trans = mean g -
+    rot mean e; the error of a frame is |rot e + trans - g|.  -> {"compared_pose_pairs", "absolute_translational_error.rmse" /
+    ".mean" / ".median" / ".std" / ".min" / ".max", "rot" [3,3], "trans" [3]}.  The reference's time-stamp association is the
+    identity here (its stamps are the frame indices) and nothing is plotted.  Fewer than two valid pairs raise ValueError."""
+    to_np = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float64)
+    g, e = to_np(gt_c2w).reshape(-1, 4, 4), to_np(est_c2w).reshape(-1, 4, 4)
+    if g.shape != e.shape:
+        raise ValueError(f"evaluate_ate: {g.shape[0]} ground-truth poses and {e.shape[0]} estimated poses")
+    keep = np.isfinite(g).all(axis=(1, 2))
+    gp, ep = g[keep, :3, 3] / float(scale), e[keep, :3, 3] / float(scale)
+    if gp.shape[0] < 2:
+        raise ValueError(f"evaluate_ate: {gp.shape[0]} valid pose pairs (at least 2 are needed)")
+    mg, me = gp.mean(0), ep.mean(0)
+    Wm = (ep - me).T @ (gp - mg)
+    U, _, Vt = np.linalg.svd(Wm.T)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2, 2] = -1.0
+    rot = U @ S @ Vt
+    trans = mg - rot @ me
+    err = np.sqrt((((ep @ rot.T) + trans - gp) ** 2).sum(1))
+    return {"compared_pose_pairs": int(err.shape[0]),
+            "absolute_translational_error.rmse": float(np.sqrt(err @ err / err.shape[0])),
+            "absolute_translational_error.mean": float(err.mean()), "absolute_translational_error.median": float(np.median(err)),
+            "absolute_translational_error.std": float(err.std()), "absolute_translational_error.min": float(err.min()),
+            "absolute_translational_error.max": float(err.max()), "rot": rot, "trans": trans}

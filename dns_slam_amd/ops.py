@@ -1124,3 +1124,144 @@ def frustum_seen(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: fl
     seen = torch.empty(P, dtype=torch.uint8, device=pts.device)
     check(lib.dns_frustum_seen(ptr(pts), P, ptr(w), K, int(H), int(W), intr, ptr(seen), stream_ptr()), "dns_frustum_seen")
     return seen.bool()
+
+
+# ----------------------------------------------------------------------------- 2-D evaluation (csrc/image_metrics.hip)
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MS_SSIM_MIN_SIDE = 160                 # DNS_MS_SSIM_MIN_SIDE: min(H, W) must be larger
+CONFUSION_LDS_CLASSES = 64             # DNS_CONFUSION_LDS_CLASSES: up to here the LDS histogram, above it global integer atomics
+
+
+def ms_ssim_window() -> torch.Tensor:
+    """The eleven fp32 window values the library filters with (host tensor)."""
+    w = (C.c_float * 11)()
+    _rawlib.dns_ms_ssim_window(w)
+    return torch.tensor(list(w), dtype=torch.float32)
+
+
+def _ms_ssim_arguments(pred, gt, depth):
+    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
+        raise ValueError("ms_ssim: pred and gt must be tensors")
+    if pred.shape != gt.shape:
+        raise ValueError(f"ms_ssim: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+    if pred.dim() not in (3, 4) or pred.shape[-1] != 3:
+        raise ValueError(f"ms_ssim: images must be [H,W,3] or [F,H,W,3], got {tuple(pred.shape)}")
+    single = pred.dim() == 3
+    F, H, W = (1,) + tuple(pred.shape[:2]) if single else tuple(pred.shape[:3])
+    if depth is not None and (not isinstance(depth, torch.Tensor) or tuple(depth.shape) != tuple(pred.shape[:-1])):
+        raise ValueError(f"ms_ssim: depth must be {tuple(pred.shape[:-1])}, got "
+                         f"{tuple(depth.shape) if isinstance(depth, torch.Tensor) else type(depth)}")
+    if min(H, W) <= MS_SSIM_MIN_SIDE:
+        raise ValueError(f"ms_ssim: images of {H} x {W}: the smaller side must be larger than {MS_SSIM_MIN_SIDE} "
+                         f"(four 2x poolings ahead of an 11-tap window)")
+    if F == 0:
+        raise ValueError("ms_ssim: no frames")
+    p = pred.detach().float().contiguous()
+    g = gt.detach().float().contiguous()
+    d = None if depth is None else depth.detach().float().contiguous()
+    require_cuda(p, g, d)
+    return p, g, d, single, int(F), int(H), int(W)
+
+
+def _ms_ssim_torch(p, g, d, F, H, W):
+    """The definition of include/dns_hip.h out of torch ops in fp32 (conv2d, avg_pool2d), for comparison and timing."""
+    import torch.nn.functional as Fn
+    win = ms_ssim_window().to(p.device)
+    x, y = p.permute(0, 3, 1, 2), g.permute(0, 3, 1, 2)
+    kh, kw = win.view(1, 1, 11, 1).repeat(3, 1, 1, 1), win.view(1, 1, 1, 11).repeat(3, 1, 1, 1)
+    filt = lambda t: Fn.conv2d(Fn.conv2d(t, kh, groups=3), kw, groups=3)
+    terms = []
+    for l in range(5):
+        mx, my = filt(x), filt(y)
+        sxx, syy, sxy = filt(x * x) - mx * mx, filt(y * y) - my * my, filt(x * y) - mx * my
+        cs = (2 * sxy + 0.03 ** 2) / (sxx + syy + 0.03 ** 2)
+        if l < 4:
+            terms.append(cs.flatten(2).mean(-1))
+            pad = (x.shape[2] % 2, x.shape[3] % 2)
+            x, y = Fn.avg_pool2d(x, 2, padding=pad), Fn.avg_pool2d(y, 2, padding=pad)
+        else:
+            terms.append(((2 * mx * my + 0.01 ** 2) / (mx * mx + my * my + 0.01 ** 2) * cs).flatten(2).mean(-1))
+    levels = torch.stack(terms, 1).double()                                   # [F,5,3]
+    wts = torch.tensor(MS_SSIM_WEIGHTS, dtype=torch.float64, device=p.device).view(1, 5, 1)
+    val = torch.prod(torch.relu(levels) ** wts, 1).mean(1)
+    sq = (p - g).double() ** 2
+    if d is None:
+        n_valid = torch.full((F,), H * W, dtype=torch.int64, device=p.device)
+        mse = sq.flatten(1).sum(1) / (3.0 * n_valid)
+    else:
+        m = d > 0
+        n_valid = m.flatten(1).sum(1)
+        mse = (sq * m[..., None]).flatten(1).sum(1) / (3.0 * n_valid)
+    return val, mse, n_valid, levels
+
+
+def ms_ssim_launch(pred: torch.Tensor, gt: torch.Tensor, depth: Optional[torch.Tensor] = None, method: str = "fused"):
+    """``ms_ssim`` without a host read: -> (ms_ssim [F] float64, mse [F] float64, n_valid [F] int64, levels [F,5,3] float64), all
+    on the device; F = 1 for [H,W,3] images."""
+    if method not in ("fused", "torch"):
+        raise ValueError(f"ms_ssim: method must be 'fused' or 'torch', got {method!r}")
+    p, g, d, _, F, H, W = _ms_ssim_arguments(pred, gt, depth)
+    if method == "torch":
+        return _ms_ssim_torch(p.view(F, H, W, 3), g.view(F, H, W, 3), None if d is None else d.view(F, H, W), F, H, W)
+    ws_b = int(_rawlib.dns_ms_ssim_ws_bytes(F, H, W))
+    if ws_b == 0:
+        raise ValueError(f"ms_ssim: {F} frames of {H} x {W} are refused (at most 65535 frames, sides <= 32768)")
+    dev = p.device
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    val = torch.empty(F, dtype=torch.float64, device=dev)
+    mse = torch.empty(F, dtype=torch.float64, device=dev)
+    n_valid = torch.empty(F, dtype=torch.int64, device=dev)
+    levels = torch.empty(F, 5, 3, dtype=torch.float64, device=dev)
+    check(lib.dns_ms_ssim(ptr(p), ptr(g), ptr(d), F, H, W, ptr(ws), ptr(val), ptr(mse), ptr(n_valid), ptr(levels), stream_ptr()),
+          "dns_ms_ssim")
+    return val, mse, n_valid, levels
+
+
+def ms_ssim(pred: torch.Tensor, gt: torch.Tensor, depth: Optional[torch.Tensor] = None, method: str = "fused"):
+    """``pytorch_msssim.ms_ssim(data_range=1.0, size_average=True)`` (eval_2d.py:302) and the masked MSE of eval_2d.py:299 for
+    image pairs pred, gt [H,W,3] or [F,H,W,3] fp32 on the device, in the project's image layout (include/dns_hip.h has the
+    definition) -> {"ms_ssim", "mse": float64 [F] (0-d for one image), "n_valid": int64, "levels": float64 [F,5,3] ([5,3])}, device
+    tensors.  ``depth`` [H,W] / [F,H,W]: the MSE runs over the pixels with depth > 0 (all pixels without it; NaN where none is
+    valid).  ``method="torch"`` composes the same definition from torch ops in fp32.  min(H, W) <= 160, mismatched shapes and CPU
+    tensors raise ValueError before anything is launched."""
+    single = isinstance(pred, torch.Tensor) and pred.dim() == 3
+    val, mse, n_valid, levels = ms_ssim_launch(pred, gt, depth, method)
+    if single:
+        val, mse, n_valid, levels = val[0], mse[0], n_valid[0], levels[0]
+    return {"ms_ssim": val, "mse": mse, "n_valid": n_valid, "levels": levels}
+
+
+def _labels_int32(t, n_class):
+    """Label image -> int32 on the device; whatever is not an integer in [0, n_class) (fractions, NaN, out of range) becomes -1."""
+    ok = (t >= 0) & (t < n_class)
+    if t.is_floating_point():
+        ok = ok & (t == torch.floor(t))
+    elif t.dtype == torch.bool:
+        t = t.to(torch.int32)
+    return torch.where(ok, t, torch.full_like(t, -1)).to(torch.int32).contiguous()
+
+
+def label_confusion(gt: torch.Tensor, pred: torch.Tensor, n_class: int):
+    """Confusion matrix of label images gt, pred of one shape on the device: [N] or [H,W] (one pair) -> (conf [n_class,n_class]
+    int64, n_invalid 0-d int64); [F,H,W] (F pairs) -> (conf [F,n_class,n_class], n_invalid [F]).  conf[g,p] counts the pixels with
+    gt g and pred p; a pixel whose gt or pred is not an integer in [0, n_class) is counted in n_invalid only.  Integer and
+    floating-point label images are accepted (``frames["gt_label"]`` is float, ``render_frame``'s arg-max int64); the conversion
+    to int32 runs on the device.  No host read."""
+    if not isinstance(gt, torch.Tensor) or not isinstance(pred, torch.Tensor):
+        raise ValueError("label_confusion: gt and pred must be tensors")
+    require_cuda(gt.contiguous(), pred.contiguous())
+    if gt.shape != pred.shape or gt.dim() not in (1, 2, 3):
+        raise ValueError(f"label_confusion: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} must share a shape [N], [H,W] or [F,H,W]")
+    nc = int(n_class)
+    if not 1 <= nc <= 4096:
+        raise ValueError(f"label_confusion: n_class {n_class} (must be 1..4096)")
+    batched = gt.dim() == 3
+    F = int(gt.shape[0]) if batched else 1
+    if F > 65535:
+        raise ValueError(f"label_confusion: {F} frames (must be <= 65535)")
+    g, p = _labels_int32(gt.detach(), nc), _labels_int32(pred.detach(), nc)
+    N = g.numel() // F if F else 0
+    conf = torch.empty(F, nc, nc, dtype=torch.int64, device=g.device)
+    n_invalid = torch.empty(F, dtype=torch.int64, device=g.device)
+    check(lib.dns_label_confusion(ptr(g), ptr(p), F, N, nc, ptr(conf), ptr(n_invalid), stream_ptr()), "dns_label_confusion")
+    return (conf, n_invalid) if batched else (conf[0], n_invalid[0])

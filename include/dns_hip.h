@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 16
+#define DNS_ABI_VERSION 17
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -717,6 +717,44 @@ int dns_icp_point_to_point(const float* src, uint32_t N, const float* tgt, uint3
  * cx, cy).  K = 0 sees nothing. */
 int dns_frustum_seen(const float* pts, uint32_t P, const float* w2c, uint32_t K, int H, int W, const float* intr, uint8_t* seen,
                      void* stream);
+
+/* ---- 2-D evaluation (eval_2d.py of the reference; csrc/image_metrics.hip; ABI v17) --------------------------------------------
+ * dns_ms_ssim: MS-SSIM and masked MSE of F image pairs pred, gt [F,H,W,3] fp32 (the project's image layout), as ONE fixed
+ * sequence of 10 launches on the stream for any F, with no host read and no floating-point atomics: every output is the same
+ * bits for every call.  The definition is pytorch_msssim.ms_ssim(data_range=1.0, size_average=True) with its defaults:
+ *   - window g[k] = exp(-(k-5)^2 / (2 1.5^2)), k = 0..10, normalised to sum 1 in fp32 (dns_ms_ssim_window returns the eleven
+ *     fp32 values the library uses [host]); a separable VALID convolution G* along H, then W, per channel: a level of h x w pixels
+ *     has (h-10) x (w-10) outputs;
+ *   - per level mu_x = G*X, mu_y = G*Y, s_xx = G*(X X) - mu_x^2, s_yy = G*(Y Y) - mu_y^2, s_xy = G*(X Y) - mu_x mu_y,
+ *     cs = (2 s_xy + C2) / (s_xx + s_yy + C2), ssim = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1) cs, C1 = 0.01^2, C2 = 0.03^2,
+ *     each averaged over the level's outputs per channel;
+ *   - between levels a 2x2 average pool, stride 2, zero padding of size % 2 on each axis (padded zeros count in the divisor 4):
+ *     output i covers the sources 2i - p and 2i - p + 1, the pooled size is (s + 2 (s % 2) - 2) / 2 + 1;
+ *   - ms_ssim = mean over the 3 channels of prod_l relu(term_l)^w_l, w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), term = cs at
+ *     levels 0..3 and ssim at level 4.
+ * The pixels and the pooled pixels are fp32, everything computed from them float64.
+ *   depth [F,H,W] fp32 or NULL: mse[f] = the mean of (pred - gt)^2 (the fp32 difference, squared and summed in float64) over the
+ *     three channels of the pixels with depth > 0 -- every pixel without depth; n_valid[f] = the number of those pixels; a frame
+ *     without one has mse = NaN (as torch's mse_loss of an empty selection).
+ *   ms_ssim [F], mse [F] float64; n_valid [F] int64; levels [F,5,3] float64: the per-level, per-channel means before relu.
+ *   dns_ms_ssim_ws_bytes: bytes of workspace (the pooled levels and one row of partial sums per workgroup); 0: refused size.
+ * min(H, W) <= DNS_MS_SSIM_MIN_SIDE is refused (DNS_E_ARG, nothing launched), as the library asserts; so are F = 0, F > 65535 and
+ * sides > 32768. */
+#define DNS_MS_SSIM_MIN_SIDE 160u
+void dns_ms_ssim_window(float* window);
+uint64_t dns_ms_ssim_ws_bytes(uint32_t F, uint32_t H, uint32_t W);
+int dns_ms_ssim(const float* pred, const float* gt, const float* depth, uint32_t F, uint32_t H, uint32_t W, void* ws, double* ms_ssim,
+                double* mse, int64_t* n_valid, double* levels, void* stream);
+
+/* dns_label_confusion: confusion matrices of F label-image pairs gt, pred [F,N] int32: conf [F,n_class,n_class] int64, rows = gt,
+ * conf[f,g,p] = the number of pixels of frame f with gt g and pred p; n_invalid [F] int64 = the pixels whose gt or pred lies outside
+ * [0, n_class), which are counted there and nowhere else.  Both outputs are cleared by the call.  n_class <=
+ * DNS_CONFUSION_LDS_CLASSES: a histogram in LDS per workgroup of 4096 pixels, flushed with 64-bit integer atomics; above it 64-bit
+ * integer atomics on conf directly.  Integer sums: exact and the same for every call on both paths. */
+#define DNS_CONFUSION_LDS_CLASSES 64u
+#define DNS_CONFUSION_MAX_CLASSES 4096u
+int dns_label_confusion(const int32_t* gt, const int32_t* pred, uint32_t F, uint64_t N, uint32_t n_class, int64_t* conf,
+                        int64_t* n_invalid, void* stream);
 
 #ifdef __cplusplus
 }
