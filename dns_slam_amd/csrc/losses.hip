@@ -155,9 +155,11 @@ __device__ __forceinline__ void loss_point_elem(const LossCfg& c, float f, float
   }
 }
 
-// One aligned float4 of the flat arrays.  Every side load (validity of the <= 2 rays it touches, z / depth of the at
-// most one point whose last channel it holds: L > 4) is issued up front on clamped indices, so nothing in the
-// arithmetic below waits on a dependent load.
+// One aligned float4 of the flat arrays, for L >= 4 ONLY (the caller walks narrower latents element by element): the quad
+// then touches at most two points and two rays and holds the last channel of at most one point, and when it does, that
+// point is p0 (p1's last channel lies at offset 2L - 1 - k0 >= L >= 4).  Every side load (validity of
+// the <= 2 rays, z / depth of that one point) is issued up front on clamped indices, so nothing in the arithmetic below
+// waits on a dependent load.
 __device__ __forceinline__ void loss_point_quad(const LossCfg& c, uint32_t e0, const float4& f4, const float4& c4,
                                                 const float* __restrict__ z, const float* __restrict__ gt_depth,
                                                 const uint8_t* __restrict__ valid, PointAcc& a) {
@@ -208,7 +210,8 @@ __global__ __launch_bounds__(256) void loss_point_sums_kernel(LossCfg c, const f
   PointAcc a = {0.f, 0.f, 0.f, 0.f, 0.f};
   const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x, gstride = gridDim.x * blockDim.x;
   const bool vec = ((((uintptr_t)fine) | ((uintptr_t)coarse)) & 15u) == 0;
-  const uint32_t Q = vec ? E / 4u : 0u;
+  // L < 4: a quad would hold several points' last channels (and up to four rays); those latents take the element walk
+  const uint32_t Q = (vec && c.L >= 4u) ? E / 4u : 0u;
   const float4* __restrict__ f4p = reinterpret_cast<const float4*>(fine);
   const float4* __restrict__ c4p = reinterpret_cast<const float4*>(coarse);
   for (uint32_t q = gtid; q < Q; q += 4u * gstride) {
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(256) void loss_point_sums_kernel(LossCfg c, const f
     for (int u = 0; u < 4; ++u)
       if (qq[u] < Q) loss_point_quad(c, 4u * qq[u], fv[u], cv[u], z, gt_depth, valid, a);
   }
-  for (uint32_t e = 4u * Q + gtid; e < E; e += gstride) {      // unaligned arrays / the last E % 4 elements
+  for (uint32_t e = 4u * Q + gtid; e < E; e += gstride) {      // unaligned arrays / L < 4 / the last E % 4 elements
     const uint32_t p = e / c.L, k = e - p * c.L;
     loss_point_elem(c, fine[e], coarse[e], p, k, p / c.S, z, gt_depth, valid, a);
   }
@@ -252,8 +255,8 @@ __device__ __forceinline__ void finalize_terms(const LossCfg& c, const float* su
   if (!c.tracker) {
     lt = sums[S_LT] / (np * (float)c.L);
     flag = (sums[S_NFRONT] > 0.f && sums[S_NOMASK] > 0.f) ? 1.f : 0.f;   // utils/common.py:794
-    fs = flag * sums[S_FS] / np;
-    op = flag * sums[S_OP] / np;
+    fs = flag > 0.f ? sums[S_FS] / np : 0.f;             // flag off: the constants 0 of utils/common.py:799-800, also when
+    op = flag > 0.f ? sums[S_OP] / np : 0.f;             // no ray is valid (np == 0: 0 * 0 / 0 would be NaN)
   }
   out[O_P] = p; out[O_D] = d; out[O_L] = l; out[O_LT] = lt; out[O_FS] = fs; out[O_OP] = op;
   out[O_TOTAL] = c.lambda_p * p + c.lambda_d * d + c.lambda_l * l + c.lambda_lt * lt + c.lambda_fs * fs + c.lambda_op * op;
@@ -465,7 +468,7 @@ __global__ __launch_bounds__(256) void loss_point_bwd_kernel(LossCfg c, const fl
         float df;
         elem(p, k, n, ok, fv[j], cv[j], df, dcv[j]);
         d_fine[(size_t)p * ldd_fine + k] = df;
-        if (++k == c.L) {                                  // next point (at most once per quad: L > 4 is not required, just likely)
+        if (++k == c.L) {                                  // next point (checked after every element: any L >= 1)
           k = 0;
           ++p;
           if (++sidx == c.S) {

@@ -52,16 +52,14 @@ class FusedAdam:
                 gr = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 m, v = self.state[p]
                 items.append((p, gr, m, v, lr))
-        for i in range(0, len(items), 32):
-            chunk = items[i:i + 32]
-            arr = (DnsAdamTensor * len(chunk))()
-            for k, (p, gr, m, v, lr) in enumerate(chunk):
-                arr[k].p, arr[k].g, arr[k].m, arr[k].v = p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr()
-                arr[k].n, arr[k].lr = p.numel(), lr
-            # one step count for all chunks: only the first chunk of a step ticks it
-            st = self._dev_state if i == 0 else self._dev_state_view()
-            check(lib.dns_adam_step(arr, len(chunk), self.betas[0], self.betas[1], self.eps, ptr(st), stream_ptr()),
-                  "dns_adam_step")
-
-    def _dev_state_view(self):
-        raise ValueError("FusedAdam: more than 32 parameter tensors per step are not supported")
+        if len(items) > 32:
+            # refused BEFORE anything is launched: parameters, moments and the device step count stay as they are
+            raise ValueError("FusedAdam: more than 32 parameter tensors per step are not supported")
+        if not items:
+            return
+        arr = (DnsAdamTensor * len(items))()
+        for k, (p, gr, m, v, lr) in enumerate(items):
+            arr[k].p, arr[k].g, arr[k].m, arr[k].v = p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr()
+            arr[k].n, arr[k].lr = p.numel(), lr
+        check(lib.dns_adam_step(arr, len(items), self.betas[0], self.betas[1], self.eps, ptr(self._dev_state), stream_ptr()),
+              "dns_adam_step")
