@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class DnsGridMeta(C.Structure):
@@ -139,6 +139,11 @@ SIGNATURES = {
     "dns_ms_ssim_ws_bytes": (C.c_uint64, [_U, _U, _U]),
     "dns_ms_ssim": (C.c_int, [_P, _P, _P, _U, _U, _U, _P, _P, _P, _P, _P, _P]),
     "dns_label_confusion": (C.c_int, [_P, _P, _U, C.c_uint64, _U, _P, _P, _P]),
+    "dns_rasterize_ws_bytes": (C.c_uint64, [_U, _U, _U, _U]),
+    "dns_rasterize_depth": (C.c_int, [_P, _U, _P, _U, _P, _U, _U, _U, C.POINTER(C.c_float), C.c_float, C.c_float, _U, _U, _P, _P,
+                                      _P, _P]),
+    "dns_depth_l1": (C.c_int, [_P, _P, _U, _U, _U, _P, _P, _P]),
+    "dns_views_see_any": (C.c_int, [_P, _U, _P, _U, _I, _I, C.POINTER(C.c_float), _P, _P]),
 }
 
 

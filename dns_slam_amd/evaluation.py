@@ -13,6 +13,11 @@ images (``ops.ms_ssim``: MS-SSIM and the masked MSE in one launch sequence), ``s
 with one host read at the end, and ``evaluate_ate`` the absolute trajectory error after the closed-form rigid alignment.  LPIPS is
 not computed: it needs AlexNet and the LPIPS linear-layer weights, which this repository does not ship; the result dict has no
 ``lpips`` key.
+
+Depth L1: the reference's ``eval_3d.calc_2d_metric``.  ``view_box`` / ``look_at`` / ``sample_views`` draw the virtual cameras
+(``ops.views_see_any`` rejects those that see the unseen cloud), ``render_depth`` turns a mesh into depth images
+(``ops.rasterize_depth`` in place of open3d's visualiser), ``depth_l1`` is the per-view mean absolute difference of two meshes'
+images (``ops.depth_l1``) with one host read at the end, and ``calc_2d_metric`` the reference's function under its own name.
 """
 from __future__ import annotations
 
@@ -390,3 +395,156 @@ def evaluate_ate(gt_c2w, est_c2w, scale=1.0) -> dict:
             "absolute_translational_error.mean": float(err.mean()), "absolute_translational_error.median": float(np.median(err)),
             "absolute_translational_error.std": float(err.std()), "absolute_translational_error.min": float(err.min()),
             "absolute_translational_error.max": float(err.max()), "rot": rot, "trans": trans}
+
+
+# ------------------------------------------------------------------------------------------- Depth L1 (eval_3d.py:120-210)
+DEPTH_L1_CAM = dict(H=500, W=500, fx=300.0, fy=300.0, cx=249.5, cy=249.5)     # calc_2d_metric: focal 300, cx = H/2 - 0.5, cy = W/2 - 0.5
+DEPTH_STACK_BUDGET = 512 << 20         # bytes the two depth stacks of one chunk of views may take (256 views at 500 x 500)
+
+
+def _host64(a):
+    return (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float64)
+
+
+def view_box(verts):
+    """get_cam_position (eval_3d.py:120-128) -> (extents float64 [3], transform float64 [4,4]): the box cameras are drawn from.
+    The reference takes trimesh's minimum-volume ORIENTED bounding box of the ground-truth mesh; that search is not available
+    here, and this function takes the AXIS-ALIGNED box of the vertices instead (the two agree for a room whose walls follow the
+    axes; pass your own ``(extents, transform)`` to ``sample_views`` otherwise).  Then, as the reference: extents scaled by (0.3,
+    0.7, 0.7), the transform (box frame -> world: the translation to the box centre) with +0.4 on its z translation."""
+    v = _host64(verts).reshape(-1, 3)
+    if not len(v) or not np.isfinite(v).all():
+        raise ValueError("view_box: no vertices, or a non-finite coordinate")
+    lo, hi = v.min(0), v.max(0)
+    extents = (hi - lo) * np.array([0.3, 0.7, 0.7])
+    transform = np.eye(4)
+    transform[:3, 3] = 0.5 * (lo + hi)
+    transform[2, 3] += 0.4
+    return extents, transform
+
+
+def look_at(origin, target, up=(0.0, 0.0, -1.0)):
+    """viewmatrix (eval_3d.py:15-21) as a 4x4 camera-to-world matrix (float64): the camera at ``origin`` looks at ``target``; z =
+    normalize(target - origin), x = normalize(up x z), y = normalize(z x x) (x right, y down, z forward)."""
+    o = np.asarray(origin, np.float64).reshape(3)
+    z = np.asarray(target, np.float64).reshape(3) - o
+    z = z / np.linalg.norm(z)
+    x = np.cross(np.asarray(up, np.float64).reshape(3), z)
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    y = y / np.linalg.norm(y)
+    m = np.eye(4)
+    m[:3, 0], m[:3, 1], m[:3, 2], m[:3, 3] = x, y, z, o
+    return m
+
+
+def _draw_views(rs, extents, transform, k):
+    """k candidate poses in draw order: per candidate rand(3) for the origin, then uniform(-10000, 10000, 3) for the target."""
+    out = np.empty((k, 4, 4))
+    for i in range(k):
+        origin = transform[:3, :3] @ ((rs.rand(3) - 0.5) * extents) + transform[:3, 3]
+        target = np.round(rs.uniform(-10000.0, 10000.0, 3), 2)
+        out[i] = look_at(origin, target)
+    return out
+
+
+def sample_views(extents, transform, n, unseen_pts=None, cam=None, seed=0, batch=256):
+    """The view sampler of calc_2d_metric (eval_3d.py:159-178) -> c2w float64 [n,4,4] (numpy).  Origin: uniform in the box, as
+    trimesh.sample.volume_rectangular draws it, (rand(3) - 0.5) * extents moved by ``transform``; target: uniform in +-10000 per
+    axis, rounded to 2 decimals; pose = ``look_at``.  All draws come from one ``numpy.random.RandomState(seed)`` (the reference
+    mixes numpy's and Python's global generators, unseeded): the same seed gives the same views.  With ``unseen_pts`` [N,3] (device
+    tensor) a candidate that sees any of them (check_proj with the intrinsics ``cam``, default ``DEPTH_L1_CAM``) is rejected:
+    candidates are drawn ``batch`` at a time (at least as many as are still needed), tested by ``ops.views_see_any`` with one
+    host read per batch, and accepted in draw order until n are.  Without ``unseen_pts`` nothing is rejected and no GPU is needed.
+    2000 batches without n accepted views raise RuntimeError."""
+    extents = np.asarray(extents, np.float64).reshape(3)
+    transform = np.asarray(transform, np.float64).reshape(4, 4)
+    n = int(n)
+    rs = np.random.RandomState(int(seed))
+    if unseen_pts is None or n == 0:
+        return _draw_views(rs, extents, transform, n)
+    cam = dict(DEPTH_L1_CAM if cam is None else cam)
+    out = np.empty((n, 4, 4))
+    got = 0
+    for _ in range(2000):
+        cand = _draw_views(rs, extents, transform, max(int(batch), n - got))
+        w2c = torch.from_numpy(world_to_camera(cand, flip_yz=True)).to(unseen_pts.device)
+        sees = ops.views_see_any(unseen_pts, w2c, cam["H"], cam["W"], cam["fx"], cam["fy"], cam["cx"], cam["cy"]).cpu().numpy()
+        ok = cand[~sees][:n - got]
+        out[got:got + len(ok)] = ok
+        got += len(ok)
+        if got == n:
+            return out
+    raise RuntimeError(f"sample_views: only {got} of {n} views accepted after 2000 batches (the unseen cloud is visible from "
+                       f"almost everywhere in the box)")
+
+
+def _depth_cam(H, W, focal, cx, cy):
+    return dict(H=int(H), W=int(W), fx=float(focal), fy=float(focal), cx=H / 2.0 - 0.5 if cx is None else float(cx),
+                cy=W / 2.0 - 0.5 if cy is None else float(cy))
+
+
+def _view_chunk(H, W, budget):
+    return max(1, int(budget) // (2 * 4 * int(H) * int(W)))
+
+
+def render_depth(verts, faces, c2w, H=500, W=500, focal=300.0, cx=None, cy=None, z_near=0.01, z_far=20.0, method="auto"):
+    """Depth images [V,H,W] fp32 on the device of the mesh from the camera-to-world poses c2w [V,4,4] (x right, y down, z
+    forward: what ``look_at`` / ``sample_views`` return), in place of open3d's visualiser (eval_3d.py:180-204): ``ops.
+    rasterize_depth`` with the reference's intrinsics as defaults (cx = H/2 - 0.5, cy = W/2 - 0.5, as the reference writes them).
+    The poses are inverted in float64 on the host and rounded to fp32.  open3d derives its near plane from the scene's bounding
+    box; here it is the parameter ``z_near``."""
+    cam = _depth_cam(H, W, focal, cx, cy)
+    w2c = torch.from_numpy(world_to_camera(c2w, flip_yz=False)).to(verts.device)
+    return ops.rasterize_depth(verts, faces, w2c, cam["H"], cam["W"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_near, z_far, method)
+
+
+def depth_l1(rec_verts, rec_faces, gt_verts, gt_faces, c2w, H=500, W=500, focal=300.0, cx=None, cy=None, z_near=0.01, z_far=20.0,
+             method="auto", budget=DEPTH_STACK_BUDGET) -> dict:
+    """The loop of eval_3d.py:180-210 over given poses c2w [V,4,4]: both meshes rendered to depth, mean |d_gt - d_rec| per view
+    over all pixels -> {"per_view": float64 array [V] (metres), "depth_l1_cm": their mean x 100}.  The views go through in chunks
+    whose two depth stacks stay under ``budget`` bytes; one host read at the end carries the per-view errors and the status words
+    (a non-finite vertex raises ValueError).  The face indices are validated up front (one host read per mesh)."""
+    cam = _depth_cam(H, W, focal, cx, cy)
+    dev = gt_verts.device
+    w2c = torch.from_numpy(world_to_camera(c2w, flip_yz=False)).to(dev)
+    V = int(w2c.shape[0])
+    if V == 0:
+        raise ValueError("depth_l1: no views")
+    for v, f in ((rec_verts, rec_faces), (gt_verts, gt_faces)):
+        ops._check_face_indices(ops._raster_arguments(v, f, w2c, cam["H"], cam["W"], method)[1], int(v.shape[0]))
+    step = _view_chunk(cam["H"], cam["W"], budget)
+    errs, stats = [], []
+    args = (cam["H"], cam["W"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_near, z_far, method)
+    for lo in range(0, V, step):
+        d_gt, s_gt = ops.rasterize_depth_launch(gt_verts, gt_faces, w2c[lo:lo + step], *args)
+        d_rec, s_rec = ops.rasterize_depth_launch(rec_verts, rec_faces, w2c[lo:lo + step], *args)
+        errs.append(ops.depth_l1(d_gt, d_rec))
+        stats += [s_gt[:1], s_rec[:1]]
+    host = torch.cat(errs + [s.double() for s in stats]).cpu().numpy()
+    if host[V:].any():
+        raise ValueError("depth_l1: non-finite coordinate in a mesh")
+    per = host[:V].copy()
+    return {"per_view": per, "depth_l1_cm": float(per.mean() * 100.0)}
+
+
+def calc_2d_metric(rec_verts, rec_faces, gt_verts, gt_faces, align=True, n_imgs=1000, unseen_pts=None, seed=0, threshold=0.1,
+                   box=None, H=500, W=500, focal=300.0, z_near=0.01, z_far=20.0, method="auto", budget=DEPTH_STACK_BUDGET) -> dict:
+    """calc_2d_metric (eval_3d.py:131-210) under its own name: with ``align`` the reconstruction is first registered to the ground
+    truth (``align_transformation`` / ``apply_transform``, as ``calc_3d_metric``); ``n_imgs`` views are drawn inside ``box`` =
+    (extents, transform) (default ``view_box(gt_verts)``) by ``sample_views`` (rejecting those that see ``unseen_pts``, the
+    reference's ``*_pc_unseen.npy`` cloud, when given); then ``depth_l1`` -> its dict plus "c2w" (the views) and
+    "transformation"."""
+    if align:
+        T = align_transformation(rec_verts, gt_verts, threshold)
+        rec_verts = apply_transform(rec_verts, T)
+    else:
+        T = torch.eye(4, dtype=torch.float64, device=rec_verts.device)
+    extents, transform = view_box(gt_verts) if box is None else box
+    cam = _depth_cam(H, W, focal, None, None)
+    c2w = sample_views(extents, transform, n_imgs, unseen_pts=unseen_pts, cam=cam, seed=seed)
+    out = depth_l1(rec_verts, rec_faces, gt_verts, gt_faces, c2w, H=H, W=W, focal=focal, z_near=z_near, z_far=z_far, method=method,
+                   budget=budget)
+    out["c2w"] = c2w
+    out["transformation"] = T
+    return out

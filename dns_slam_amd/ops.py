@@ -1265,3 +1265,123 @@ def label_confusion(gt: torch.Tensor, pred: torch.Tensor, n_class: int):
     n_invalid = torch.empty(F, dtype=torch.int64, device=g.device)
     check(lib.dns_label_confusion(ptr(g), ptr(p), F, N, nc, ptr(conf), ptr(n_invalid), stream_ptr()), "dns_label_confusion")
     return (conf, n_invalid) if batched else (conf[0], n_invalid[0])
+
+
+# ----------------------------------------------------------------------------- Depth L1 (csrc/mesh_raster.hip)
+RASTER_SMALL_BOX = 8                   # RS_SMALL: the largest pixel box a set-up thread draws itself
+DEPTH_L1_PARTS = 64                    # DNS_DEPTH_L1_PARTS
+RASTER_METHODS = ("auto", "simple")
+
+
+def _raster_arguments(verts, faces, w2c, H, W, method):
+    if not all(isinstance(t, torch.Tensor) for t in (verts, faces, w2c)):
+        raise ValueError("rasterize_depth: verts, faces and w2c must be tensors")
+    v = verts.detach().contiguous().float()
+    f = faces.detach().contiguous()
+    w = w2c.detach().contiguous().float()
+    require_cuda(v, f, w)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or w.dim() != 3 or w.shape[1:] != (4, 4):
+        raise ValueError(f"rasterize_depth: verts [P,3], faces [F,3] and w2c [V,4,4], got {tuple(v.shape)}, {tuple(f.shape)} and "
+                         f"{tuple(w.shape)}")
+    if f.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"rasterize_depth: faces must be int32 or int64, got {f.dtype}")
+    if method not in RASTER_METHODS:
+        raise ValueError(f"rasterize_depth: method must be one of {RASTER_METHODS}, got {method!r}")
+    if not (1 <= int(H) <= 32768 and 1 <= int(W) <= 32768):
+        raise ValueError(f"rasterize_depth: image {H} x {W} (sides must be 1..32768)")
+    return v, f, w
+
+
+def _check_face_indices(f, P):
+    """ValueError when a face holds an index outside [0, P) (one host read)."""
+    if f.numel():
+        lo, hi = (int(x) for x in torch.stack((f.min(), f.max())).cpu().tolist())
+        if lo < 0 or hi >= P:
+            raise ValueError(f"rasterize_depth: a face holds a vertex index outside [0, {P}) (min {lo}, max {hi})")
+
+
+def rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near=0.01, z_far=20.0, method="auto", stats=False,
+                           list_cap=0):
+    """``rasterize_depth`` without its host reads: -> (depth [V,H,W] fp32, status [4] int32 on the device; include/dns_hip.h).
+    The face indices are NOT validated here (a face with an index outside [0, P) is skipped by the kernel and flagged in
+    status[0] bit 1); int64 faces must fit int32.  ``list_cap``: pairs per launch (0: the library's default)."""
+    v, f, w = _raster_arguments(verts, faces, w2c, H, W, method)
+    f = f.to(torch.int32)
+    zn, zf = float(z_near), float(z_far)
+    if not (zn > 0.0 and zf >= zn and math.isfinite(zf)):
+        raise ValueError(f"rasterize_depth: need 0 < z_near <= z_far < inf, got {z_near!r}, {z_far!r}")
+    if not (all(math.isfinite(float(x)) for x in (fx, fy, cx, cy)) and float(fx) != 0.0 and float(fy) != 0.0):
+        raise ValueError("rasterize_depth: the intrinsics must be finite, fx and fy non-zero")
+    P, F, V = int(v.shape[0]), int(f.shape[0]), int(w.shape[0])
+    dev = v.device
+    depth = torch.empty(V, int(H), int(W), dtype=torch.float32, device=dev)
+    status = torch.zeros(4, dtype=torch.int32, device=dev)
+    if V == 0:
+        return depth, status
+    ws_b = int(_rawlib.dns_rasterize_ws_bytes(F, V, int(H), int(W)))
+    if ws_b == 0:
+        raise ValueError(f"rasterize_depth: {F} faces at {H} x {W} are refused (F >= 2^31)")
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    intr = (C.c_float * 4)(float(fx), float(fy), float(cx), float(cy))
+    flags = (1 if method == "simple" else 0) | (2 if stats else 0)
+    check(lib.dns_rasterize_depth(ptr(v), P, ptr(f), F, ptr(w), V, int(H), int(W), intr, zn, zf, flags, int(list_cap), ptr(ws),
+                                  ptr(depth), ptr(status), stream_ptr()), "dns_rasterize_depth")
+    return depth, status
+
+
+def rasterize_depth(verts: torch.Tensor, faces: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: float, fy: float, cx: float,
+                    cy: float, z_near: float = 0.01, z_far: float = 20.0, method: str = "auto", return_stats: bool = False):
+    """Depth images of a triangle mesh: verts [P,3] fp32, faces [F,3] int32, w2c [V,4,4] fp32 world->camera in the OpenCV
+    convention (x right, y down, z forward) -> depth [V,H,W] fp32: camera-space z of the nearest surface through each pixel
+    centre (centres at integer coordinates), 0 where nothing is seen; both faces of a triangle are drawn; nothing nearer than
+    ``z_near`` or beyond ``z_far``.  The arithmetic is written out in include/dns_hip.h; the image is the same bits for every
+    call and both methods.  ``method``: "auto" (small boxes by the set-up thread, the others by a workgroup each) or "simple"
+    (every triangle by its set-up thread).  A face index outside [0, P) and CPU tensors raise ValueError (one host read for the
+    indices).  ``return_stats`` appends {"nonfinite": a triangle with a non-finite vertex was skipped, "large": (triangle, view)
+    pairs drawn through the list, "small": pairs drawn by their set-up thread} (a second host read)."""
+    v, f, _ = _raster_arguments(verts, faces, w2c, H, W, method)
+    _check_face_indices(f, int(v.shape[0]))
+    depth, status = rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near, z_far, method, stats=return_stats)
+    if not return_stats:
+        return depth
+    bad, large, small, _ = (int(x) for x in status.cpu().tolist())
+    return depth, {"nonfinite": bool(bad & 1), "large": large, "small": small}
+
+
+def depth_l1(a: torch.Tensor, b: torch.Tensor):
+    """a, b [V,H,W] fp32 on the device -> err [V] float64 = mean |a - b| over ALL pixels of each view (zeros of the background
+    included, as the reference's ``np.abs(gt_depth - ours_depth).mean()``), differences and sums in float64 in a fixed order: the
+    same bits for every call.  No host read."""
+    if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor):
+        raise ValueError("depth_l1: a and b must be tensors")
+    x, y = a.detach().contiguous().float(), b.detach().contiguous().float()
+    require_cuda(x, y)
+    if x.dim() != 3 or x.shape != y.shape:
+        raise ValueError(f"depth_l1: two stacks [V,H,W] of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    V, H, W = (int(s) for s in x.shape)
+    if V and not (1 <= H <= 32768 and 1 <= W <= 32768):
+        raise ValueError(f"depth_l1: image {H} x {W} (sides must be 1..32768)")
+    err = torch.empty(V, dtype=torch.float64, device=x.device)
+    if V == 0:
+        return err
+    partial = torch.empty(V * DEPTH_L1_PARTS, dtype=torch.float64, device=x.device)
+    check(lib.dns_depth_l1(ptr(x), ptr(y), V, H, W, ptr(partial), ptr(err), stream_ptr()), "dns_depth_l1")
+    return err
+
+
+def views_see_any(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: float, fy: float, cx: float, cy: float):
+    """points [N,3] fp32 world, w2c [K,4,4] fp32 world->camera in ``frustum_seen``'s convention -> sees [K] bool: pose k sees at
+    least one of the points, under exactly ``frustum_seen``'s projection and inequalities (``frustum_seen`` answers per point,
+    this per pose).  No host read."""
+    if not isinstance(points, torch.Tensor) or not isinstance(w2c, torch.Tensor):
+        raise ValueError("views_see_any: points and w2c must be tensors")
+    pts = points.detach().contiguous().float()
+    w = w2c.detach().contiguous().float()
+    require_cuda(pts, w)
+    if pts.dim() != 2 or pts.shape[1] != 3 or w.dim() != 3 or w.shape[1:] != (4, 4):
+        raise ValueError(f"views_see_any: points [N,3] and w2c [K,4,4], got {tuple(pts.shape)} and {tuple(w.shape)}")
+    N, K = int(pts.shape[0]), int(w.shape[0])
+    intr = (C.c_float * 4)(float(fx), float(fy), float(cx), float(cy))
+    sees = torch.empty(K, dtype=torch.uint8, device=w.device)
+    check(lib.dns_views_see_any(ptr(pts), N, ptr(w), K, int(H), int(W), intr, ptr(sees), stream_ptr()), "dns_views_see_any")
+    return sees.bool()

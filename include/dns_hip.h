@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 17
+#define DNS_ABI_VERSION 18
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -755,6 +755,48 @@ int dns_ms_ssim(const float* pred, const float* gt, const float* depth, uint32_t
 #define DNS_CONFUSION_MAX_CLASSES 4096u
 int dns_label_confusion(const int32_t* gt, const int32_t* pred, uint32_t F, uint64_t N, uint32_t n_class, int64_t* conf,
                         int64_t* n_invalid, void* stream);
+
+/* ---- Depth L1 (calc_2d_metric, eval_3d.py:120-210 of the reference; csrc/mesh_raster.hip; ABI v18) ---------------------------
+ * dns_rasterize_depth: depth [V,H,W] fp32 of the mesh verts [P,3] fp32, faces [F,3] int32 seen from the V poses w2c [V,16] fp32
+ * (row-major world->camera, OpenCV axes: x right, y down, z forward); intr [host] (fx, fy, cx, cy), pixel centres at integer
+ * coordinates.  Depth is camera-space z, the background 0, both faces of a triangle are drawn, nothing nearer than z_near or
+ * beyond z_far.  Homogeneous rasterisation, no clipping, every operation one fp32 rounding in this order:
+ *   v = ((r0 x + r1 y) + r2 z) + t per row of w2c;  d = ((j - cx) / fx, (i - cy) / fy, 1) for pixel (row i, column j);
+ *   per edge, its vertices ordered by vertex index a < b: c = v_a x v_b (c.x = a.y b.z - a.z b.y, ...), negated when the winding
+ *   runs b -> a; E = (d.x c.x + d.y c.y) + c.z; covered iff all three E >= 0 or all three E <= 0;
+ *   n = (v1 - v0) x (v2 - v0), t = ((n.x v0.x + n.y v0.y) + n.z v0.z) / ((n.x d.x + n.y d.y) + n.z), accepted iff
+ *   z_near <= t <= z_far; the pixel is the minimum of the accepted t (atomicMin on the bits), so the image is the same bits for
+ *   every call, both methods and every list_cap.
+ * A triangle with a non-finite vertex (in world or camera space) is skipped and flagged; one with n = 0 is skipped; one with an
+ * index outside [0, P) is skipped and flagged (never dereferenced).
+ *   flags: DNS_RASTER_SIMPLE = every triangle is drawn by its set-up thread (the baseline); otherwise boxes of at most 8 x 8
+ *     pixels are, and the others go through a list to one workgroup each.  DNS_RASTER_STATS = count the set-up-thread
+ *     triangles into status[2] (one atomic each: for tests and tools).
+ *   list_cap: 0, or a smaller number of (triangle, view) pairs per launch than the default 2^24 (the list always holds every pair
+ *     of a launch; a small cap means more launches -- at most 65536).
+ *   dns_rasterize_ws_bytes: bytes of workspace (0: refused size -- F >= 2^31, a side 0 or > 32768).
+ *   status [4] uint32 (device): status[0] = DNS_RASTER_NONFINITE | DNS_RASTER_BAD_INDEX bits; status[1] = (triangle, view) pairs
+ *     drawn through the list; status[2] = pairs drawn by their set-up thread (with DNS_RASTER_STATS).
+ * V = 0: nothing is launched.  F = 0: all zeros.  Needs 0 < z_near <= z_far < inf.
+ *
+ * dns_depth_l1: err [V] float64 = sum |a - b| / (H W) over ALL pixels of the stacks a, b [V,H,W] fp32 (differences and sums in
+ * float64).  partial [V * DNS_DEPTH_L1_PARTS] float64 is the caller's scratch: one strided partial sum per workgroup, added in
+ * a fixed order -- the same bits for every call.
+ *
+ * dns_views_see_any: sees [K] uint8 = pose k of w2c [K,16] sees at least one of the points pts [N,3], under the projection,
+ * epsilon and inequalities of dns_frustum_seen (w2c in its convention).  N = 0: all zeros. */
+#define DNS_RASTER_SIMPLE 1u
+#define DNS_RASTER_STATS 2u
+#define DNS_RASTER_NONFINITE 1u
+#define DNS_RASTER_BAD_INDEX 2u
+#define DNS_DEPTH_L1_PARTS 64u
+uint64_t dns_rasterize_ws_bytes(uint32_t F, uint32_t V, uint32_t H, uint32_t W);
+int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t* faces, uint32_t F, const float* w2c, uint32_t V, uint32_t H,
+                        uint32_t W, const float* intr, float z_near, float z_far, uint32_t flags, uint32_t list_cap, void* ws,
+                        float* depth, uint32_t* status, void* stream);
+int dns_depth_l1(const float* a, const float* b, uint32_t V, uint32_t H, uint32_t W, double* partial, double* err, void* stream);
+int dns_views_see_any(const float* pts, uint32_t N, const float* w2c, uint32_t K, int H, int W, const float* intr, uint8_t* sees,
+                      void* stream);
 
 #ifdef __cplusplus
 }
