@@ -3,6 +3,11 @@
 The grid query, the keyframe projection, marching cubes and the connected-components filter run on the GPU (csrc/mesh.hip,
 csrc/mesh_cc.hip, ``Mapper.eval_occupancy``); the reference's host-side numpy / skimage / trimesh steps have no counterpart
 here beyond the binary PLY writer below.
+
+A mapper trained with stem features (``mapper.encoder`` set) is meshed with ``stem=``: the vertex query then feeds the colour and
+logit networks get_2d_feature's keyframe codes (meshing.py:311-377; csrc/mesh_feature.hip, ``ops.keyframe_codes``).  The
+geometry needs no codes -- the occupancy is the coarse / fine network's, which reads only the point encoding -- so the grid
+pass, marching cubes, cleaning and the component filter are the same with and without ``stem``.
 """
 from __future__ import annotations
 
@@ -60,24 +65,64 @@ class Mesher:
         n = torch.arange(s0, s1, device=self.device)
         return torch.stack((x[(n // nz) % nx], y[n // (nx * nz)], z[n % nz]), 1)
 
-    def _keyframes(self, keyframe_dict):
+    def _keyframes(self, keyframe_dict, stem=None):
+        """(w2c, labels, max_depth) of the keyframes; with ``stem`` additionally (depths [K,H,W], origins [K,3], maps), what
+        ``ops.keyframe_codes`` reads.  ``maps`` holds ``stem`` and, for ``stem=True``, the keyframes: the [K,h,w,C] stack is
+        computed by ``_stem_maps`` when the vertex query first asks for it, not ahead of the grid pass, which never reads it."""
         dev = self.device
         c2w = torch.stack([torch.as_tensor(kf["est_c2w"]).to(dev) for kf in keyframe_dict])
         w2c = torch.inverse(c2w).float()                                     # meshing.py:208,319
         labels = torch.stack([torch.as_tensor(kf["gt_label"]).to(dev).float() for kf in keyframe_dict])
-        max_depth = torch.stack([torch.as_tensor(kf["gt_depth"]).to(dev).float().max() for kf in keyframe_dict])
-        return w2c, labels, max_depth
+        if stem is None:
+            max_depth = torch.stack([torch.as_tensor(kf["gt_depth"]).to(dev).float().max() for kf in keyframe_dict])
+            return w2c, labels, max_depth
+        if stem is not True and not (isinstance(stem, torch.Tensor) and stem.dim() == 4 and stem.shape[0] == len(keyframe_dict)):
+            raise ValueError("Mesher: stem must be True or the [K,h,w,C] stack of the keyframes' stem maps "
+                             "(Mesher.keyframe_stem)")
+        if stem is True and getattr(self.mapper, "encoder", None) is None:
+            raise ValueError("Mesher: stem=True needs mapper.encoder; pass the maps of Mesher.keyframe_stem(..., encoder=) instead")
+        depths = torch.stack([torch.as_tensor(kf["gt_depth"]).to(dev).float() for kf in keyframe_dict])
+        max_depth = depths.reshape(depths.shape[0], -1).max(1).values
+        origins = c2w[:, :3, 3].float().contiguous()                         # refer_o, meshing.py:363
+        return w2c, labels, max_depth, depths, origins, {"stem": stem, "keyframes": keyframe_dict}
 
-    def _check_supported(self):
-        if getattr(self.mapper, "encoder", None) is not None:
+    def _stem_maps(self, maps):
+        """The [K,h,w,C] stack behind the last entry of ``_keyframes(keyframe_dict, stem)``; ``stem=True`` runs the stem here,
+        once per bundle."""
+        if maps["stem"] is True:
+            maps["stem"] = self.keyframe_stem(maps["keyframes"])
+        return maps["stem"].to(self.device)
+
+    def _check_supported(self, stem=None):
+        if stem is None and getattr(self.mapper, "encoder", None) is not None:
             raise NotImplementedError("Mesher: a mapper with stem features (mapper.encoder set) needs get_2d_feature's 2-D codes "
-                                      "through Merge, which this mesher does not compute")
+                                      "through Merge; pass stem=True (or stem= the maps of Mesher.keyframe_stem) to compute them")
 
     @torch.no_grad()
-    def grid_occupancy(self, keyframe_dict, stage="fine", kf=None):
+    def keyframe_stem(self, keyframe_dict, encoder=None, batch=4):
+        """The stem maps of the keyframes' ``gt_color`` (``encoder`` or ``mapper.encoder``, ``batch`` keyframes per call) as
+        the channels-last fp32 stack [K, h, w, 64] that ``ops.keyframe_codes`` reads.  The stack stays on the device for the
+        whole extraction: K * 64 * h * w * 4 bytes, 52 MB per keyframe at Replica resolution (h x w = 340 x 600)."""
+        enc = encoder if encoder is not None else getattr(self.mapper, "encoder", None)
+        if enc is None:
+            raise ValueError("Mesher.keyframe_stem: no encoder (mapper.encoder is None and encoder= was not given)")
+        out = None
+        for s in range(0, len(keyframe_dict), batch):
+            img = torch.stack([torch.as_tensor(kf["gt_color"]).to(self.device).float() for kf in keyframe_dict[s:s + batch]])
+            f = enc(img[None])[0].float()                                    # [n, C, h, w]
+            if out is None:
+                out = torch.empty(len(keyframe_dict), f.shape[2], f.shape[3], f.shape[1], device=self.device)
+            out[s:s + f.shape[0]] = f.permute(0, 2, 3, 1)
+        return out if out is not None else torch.zeros(0, 1, 1, 64, device=self.device)
+
+    @torch.no_grad()
+    def grid_occupancy(self, keyframe_dict, stage="fine", kf=None, stem=None):
         """[nx, ny, nz] occupancy volume of the query grid (meshing.py:643-654: keyframe labels -> eval_points per
-        points_batch_size chunk -> values[:, 3]) and the grid's axes."""
-        self._check_supported()
+        points_batch_size chunk -> values[:, 3]) and the grid's axes.  ``stem`` only lifts the refusal of a mapper with an
+        encoder and is not used: the reference computes get_2d_feature's codes for every grid chunk, but they reach only the
+        colour and logit networks, and this pass keeps the occupancy alone, which the coarse / fine network forms from the
+        point encoding."""
+        self._check_supported(stem)
         kf = kf or self._keyframes(keyframe_dict)
         grid = self.get_grid_uniform()
         nx, ny, nz = (len(a) for a in grid["xyz"])
@@ -95,12 +140,13 @@ class Mesher:
         return occ.reshape(ny, nx, nz).permute(1, 0, 2).contiguous(), grid
 
     @torch.no_grad()
-    def extract(self, keyframe_dict, stage="fine", clean_mesh=True, components=None, min_area=None):
+    def extract(self, keyframe_dict, stage="fine", clean_mesh=True, components=None, min_area=None, stem=None):
         """-> (verts [V,3] fp32 world / scale, faces [F,3] int32, colors [V,3] uint8, labels [V] int64), all on the device.
         ``components``: None, "small" (keep the components whose area exceeds ``min_area``, default
         ``cfg['meshing']['remove_small_geometry_threshold'] * scale * scale``) or "largest" (meshing.py:721-733); the filter
-        runs on the cleaned mesh, ahead of the vertex query, and only with ``clean_mesh``."""
-        self._check_supported()
+        runs on the cleaned mesh, ahead of the vertex query, and only with ``clean_mesh``.  ``stem``: None (a mapper without
+        stem features), True (run ``keyframe_stem``) or the [K,h,w,C] maps: the vertex query then uses the keyframe codes."""
+        self._check_supported(stem)
         if components not in (None, "small", "largest"):
             raise ValueError(f"Mesher.extract: components must be None, 'small' or 'largest', got {components!r}")
         if components is not None and not clean_mesh:
@@ -110,8 +156,8 @@ class Mesher:
                 raise ValueError("Mesher.extract: components='small' needs cfg['meshing']['remove_small_geometry_threshold'] "
                                  "(or min_area=)")
             min_area = self.remove_small_geometry_threshold * self.scale * self.scale
-        kf = self._keyframes(keyframe_dict)
-        vol, grid = self.grid_occupancy(keyframe_dict, stage, kf)
+        kf = self._keyframes(keyframe_dict, stem)
+        vol, grid = self.grid_occupancy(keyframe_dict, stage, kf, stem)
         x, y, z = grid["xyz"]
         verts, faces = ops.marching_cubes(vol, self.level_set, (x[0], y[0], z[0]), (x[2] - x[1], y[2] - y[1], z[2] - z[1]))
         if clean_mesh and faces.shape[0]:
@@ -120,7 +166,7 @@ class Mesher:
             verts, faces = self.filter_components(verts, faces, min_area=min_area)
         elif components == "largest":
             verts, faces = self.filter_components(verts, faces, largest=True)
-        colors, labels = self.vertex_query(verts, kf, stage)
+        colors, labels = self.vertex_query(verts, kf, stage, stem)
         return verts / self.scale, faces, colors, labels
 
     def clean(self, verts, faces, kf):
@@ -147,13 +193,19 @@ class Mesher:
             keep = comp_area > float(min_area)
         return compact_mesh(verts, faces, keep)[:2]
 
-    def vertex_query(self, verts, kf, stage="fine"):
+    def vertex_query(self, verts, kf, stage="fine", stem=None):
         """meshing.py:735-753: colours (clip(rgb, 0, 1) * 255 as uint8) and labels (argmax, -1 outside the bound) at the
-        vertices, the > 1 point rule per points_batch_size chunk of vertices."""
+        vertices, the > 1 point rule per points_batch_size chunk of vertices.  With ``stem`` (``kf`` from
+        ``_keyframes(keyframe_dict, stem)``) the colour and logit networks read get_2d_feature's keyframe codes as pixel_pts."""
         if verts.shape[0] == 0:
             return (torch.zeros(0, 3, dtype=torch.uint8, device=verts.device), torch.zeros(0, dtype=torch.int64, device=verts.device))
         label, _ = ops.keyframe_project(verts, kf[0], kf[1], kf[2], self.cam)
-        values, labels = self.mapper.eval_points(verts, None, label, stage=stage, rule_chunk=self.points_batch_size)
+        codes = None
+        if stem is not None:
+            if len(kf) < 6:
+                raise ValueError("Mesher.vertex_query: stem needs the keyframe bundle of _keyframes(keyframe_dict, stem)")
+            codes, _ = ops.keyframe_codes(verts, kf[0], kf[4], kf[3], self._stem_maps(kf[5]), self.cam, self.mapper.decoder.merge)
+        values, labels = self.mapper.eval_points(verts, codes, label, stage=stage, rule_chunk=self.points_batch_size)
         colors = (values[:, :3].clamp(0, 1) * 255).to(torch.uint8)
         if labels is None:
             labels = torch.full((verts.shape[0],), -1, dtype=torch.int64, device=verts.device)
@@ -161,11 +213,11 @@ class Mesher:
 
     def get_mesh(self, mesh_out_file, keyframe_dict, idx, color=True, label=False, palette=None, show_forecast=False,
                  element=False, clean_mesh=None, stage="fine", remove_small_geometry=False, fill_holes=False, components=None,
-                 min_area=None):
+                 min_area=None, stem=None):
         """Writes ``{mesh_out_file}/mesh_{idx}.ply`` (vertex colours when ``color``, the vertex labels as an int property) and,
         with ``label`` and a ``palette`` (class -> RGB: an [n_class, 3] array, a dict or a callable like the reference's
         v_map_function), ``mesh_{idx}_semantic.ply``.  Returns the paths written.  ``components`` / ``min_area``: the
-        connected-components filter of ``extract`` (meshing.py:721-733).  fill_holes (meshing.py:770) is not implemented and,
+        connected-components filter of ``extract`` (meshing.py:721-733); ``stem``: as in ``extract``.  fill_holes (meshing.py:770) is not implemented and,
         like the reference's own spellings of the filters and of the per-class meshes, refused when asked for."""
         if show_forecast:
             raise NotImplementedError("Mesher.get_mesh: show_forecast is not supported")
@@ -178,7 +230,7 @@ class Mesher:
         if fill_holes:
             raise NotImplementedError("Mesher.get_mesh: fill_holes is not supported")
         verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh,
-                                                    components, min_area)
+                                                    components, min_area, stem)
         v, f, lab = verts.cpu().numpy(), faces.cpu().numpy(), labels.cpu().numpy()
         os.makedirs(mesh_out_file, exist_ok=True)
         out = [os.path.join(mesh_out_file, f"mesh_{idx}.ply")]
@@ -189,12 +241,13 @@ class Mesher:
         return out
 
     def get_part_meshes(self, mesh_out_file, keyframe_dict, idx, color=True, stage="fine", clean_mesh=None, components=None,
-                        min_area=None):
+                        min_area=None, stem=None):
         """The reference's ``element`` branch (meshing.py:786-825): for every distinct vertex label e of the extracted mesh,
         the faces with at least one vertex labelled e, compacted, as ``{mesh_out_file}/mesh_{idx}_part_{int(e)}.ply``.  Colours
-        and labels are those of the full mesh's vertex query, not queried again per part.  Returns the paths written."""
+        and labels are those of the full mesh's vertex query, not queried again per part.  ``stem``: as in ``extract``.  Returns
+        the paths written."""
         verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh,
-                                                    components, min_area)
+                                                    components, min_area, stem)
         os.makedirs(mesh_out_file, exist_ok=True)
         out = []
         for e in torch.unique(labels).tolist():

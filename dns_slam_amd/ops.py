@@ -956,6 +956,140 @@ def keyframe_project(points: torch.Tensor, w2c: torch.Tensor, labels: torch.Tens
     return label, seen.bool()
 
 
+# ----------------------------------------------------------------------------- keyframe codes (csrc/mesh_feature.hip)
+KF_WORKSPACE_BYTES = 1 << 30                 # default budget of keyframe_codes' row, latent, record and relative-point buffers
+
+
+def _kf_args(who, points, w2c, depths, cam, chunked=False):
+    for t in (points, w2c, depths):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: dns_slam_amd ops run on the GPU only (got a non-CUDA tensor); there is no CPU fallback")
+    if len({t.device for t in (points, w2c, depths)}) != 1:
+        raise ValueError(f"{who}: the arguments live on different devices")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{who}: points must be [P,3], got {tuple(points.shape)}")
+    if w2c.dim() != 3 or w2c.shape[1:] != (4, 4) or depths.dim() != 3 or depths.shape[0] != w2c.shape[0]:
+        raise ValueError(f"{who}: w2c [K,4,4] and depths [K,H,W] with one K, got {tuple(w2c.shape)} and {tuple(depths.shape)}")
+    if not all(t.is_floating_point() for t in (points, w2c, depths)):
+        raise ValueError(f"{who}: points, w2c and depths must be floating point")
+    pts = points.detach().contiguous().float()
+    w = w2c.detach().contiguous().float()
+    dep = depths.detach().contiguous().float()
+    K, H, W = int(w.shape[0]), int(dep.shape[1]), int(dep.shape[2])
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: depth images of {H} x {W}")
+    if not chunked and pts.shape[0] * max(K, 1) >= 1 << 31:           # (keyframe_codes launches per chunk: chunk * K is bounded there)
+        raise ValueError(f"{who}: {pts.shape[0]} points x {K} keyframes (must be < 2^31 pairs)")
+    intr = (C.c_float * 4)(float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]))
+    return pts, w, dep, K, H, W, intr
+
+
+def _kf_pair_list(pts, w, dep, K, H, W, intr, records=None):
+    """count [P] int32, offset [P] int64, n (the ONE host read) and the records [n, 4] int32 (in ``records`` when given)."""
+    P, dev = pts.shape[0], pts.device
+    count = torch.empty(P, dtype=torch.int32, device=dev)
+    check(lib.dns_kf_pair_count(ptr(pts), P, ptr(w), K, ptr(dep), H, W, intr, ptr(count), stream_ptr()), "dns_kf_pair_count")
+    incl = torch.cumsum(count, 0, dtype=torch.int64)
+    offset = incl - count
+    n = int(incl[-1].item())
+    if records is None:
+        records = torch.empty(max(n, 1), 4, dtype=torch.int32, device=dev)
+    if n > records.shape[0]:
+        raise RuntimeError(f"keyframe pairs: {n} pairs for a list of {records.shape[0]}")
+    if n:
+        check(lib.dns_kf_pair_emit(ptr(pts), P, ptr(w), K, ptr(dep), H, W, intr, ptr(offset), ptr(records), n, stream_ptr()),
+              "dns_kf_pair_emit")
+    return count, offset, n, records
+
+
+@torch.no_grad()
+def keyframe_pairs(points: torch.Tensor, w2c: torch.Tensor, depths: torch.Tensor, cam: dict):
+    """points [P,3] world, w2c [K,4,4] (torch.inverse(est_c2w) in fp32), depths [K,H,W] (gt_depth), cam {'fx','fy','cx','cy'} ->
+    (point [n] int64, keyframe [n] int64, iu [n] int64, iv [n] int64, count [P] int32): the (point, keyframe) pairs that
+    contribute to get_2d_feature's code (meshing.py:337-356: seen, and inside the truncation band of the keyframe's depth at
+    the rounded pixel (iu, iv)), point-major with the keyframes ascending within a point; count = pairs per point.  One host
+    read (n)."""
+    pts, w, dep, K, H, W, intr = _kf_args("keyframe_pairs", points, w2c, depths, cam)
+    P, dev = pts.shape[0], pts.device
+    if P == 0 or K == 0:
+        e = torch.zeros(0, dtype=torch.int64, device=dev)
+        return e, e.clone(), e.clone(), e.clone(), torch.zeros(P, dtype=torch.int32, device=dev)
+    count, _, n, rec = _kf_pair_list(pts, w, dep, K, H, W, intr)
+    rec = rec[:n].long()
+    return rec[:, 0].contiguous(), rec[:, 1].contiguous(), rec[:, 2].contiguous(), rec[:, 3].contiguous(), count
+
+
+@torch.no_grad()
+def keyframe_codes(points: torch.Tensor, w2c: torch.Tensor, origins: torch.Tensor, depths: torch.Tensor, stem_nhwc: torch.Tensor,
+                   cam: dict, merge, max_pairs: Optional[int] = None):
+    """get_2d_feature's pixel_pts (meshing.py:311-377): points [P,3] world, w2c [K,4,4], origins [K,3] (est_c2w[:3,3]), depths
+    [K,H,W], stem_nhwc [K,h,w,C] fp32 (the stem maps, channels last, half resolution), ``merge`` the ``Decoder.merge`` module
+    -> (code [P, hidden] fp32: the mean over the contributing keyframes of Merge(p - o_k, stem value at the rounded pixel), zeros
+    where none contributes; count [P] int32).  Forward only.
+
+    The points are taken in chunks of ``max_pairs // K`` (``max_pairs`` defaults to KF_WORKSPACE_BYTES over the bytes of a
+    pair: 604 for the 112 -> 32 network), so the workspace is bounded whatever the scene and only ``chunk * K`` has to stay
+    below 2^31; a point's pairs are never split and are added in keyframe order, so the result is
+    the same bits for every ``max_pairs``.  One host read (the pair total) per chunk."""
+    pts, w, dep, K, H, W, intr = _kf_args("keyframe_codes", points, w2c, depths, cam, chunked=True)
+    dev = pts.device
+    net = merge.decoder
+    n_pe, hidden = int(merge.pe_dim), int(net.n_output_dims)
+    if not (isinstance(origins, torch.Tensor) and origins.is_cuda and origins.device == dev and origins.is_floating_point()
+            and origins.shape == (K, 3)):
+        raise ValueError(f"keyframe_codes: origins must be a floating-point [K,3] = [{K},3] tensor on {dev}")
+    if not (isinstance(stem_nhwc, torch.Tensor) and stem_nhwc.is_cuda and stem_nhwc.device == dev
+            and stem_nhwc.dtype == torch.float32 and stem_nhwc.dim() == 4 and stem_nhwc.shape[0] == K):
+        raise ValueError(f"keyframe_codes: stem_nhwc must be a float32 [K,h,w,C] tensor on {dev} with K = {K}")
+    h, w_, Cc = (int(s) for s in stem_nhwc.shape[1:])
+    if Cc % 4 != 0 or Cc == 0:
+        raise ValueError(f"keyframe_codes: {Cc} stem channels (must be a multiple of 4)")
+    if n_pe + Cc != int(net.n_input_dims) or n_pe % 4 != 0 or hidden % 4 != 0:
+        raise ValueError(f"keyframe_codes: {n_pe} encoding + {Cc} stem columns for a Merge network of {net.n_input_dims} inputs")
+    if net.params.device != dev:
+        raise ValueError(f"keyframe_codes: the Merge network lives on {net.params.device}, the points on {dev}")
+    if K and (h < 1 or w_ < 1):
+        raise ValueError(f"keyframe_codes: stem maps of {h} x {w_}")
+    org = origins.detach().contiguous().float()
+    feat = stem_nhwc.detach().contiguous()
+    P = pts.shape[0]
+    code = torch.zeros(P, hidden, device=dev)
+    count = torch.zeros(P, dtype=torch.int32, device=dev)
+    if P == 0 or K == 0:
+        return code, count
+    ld = n_pe + Cc
+    if max_pairs is None:
+        max_pairs = KF_WORKSPACE_BYTES // (4 * (ld + hidden + 4 + 3))
+    max_pairs = int(max_pairs)
+    if not 1 <= max_pairs < 1 << 31:
+        raise ValueError(f"keyframe_codes: max_pairs {max_pairs}")
+    if K >= 1 << 31:
+        raise ValueError(f"keyframe_codes: {K} keyframes")
+    chunk = min(max(max_pairs // K, 1), P)
+    cap = chunk * K
+    rows = torch.empty(cap, ld, device=dev)
+    rel = torch.empty(cap, 3, device=dev)
+    records = torch.empty(cap, 4, dtype=torch.int32, device=dev)
+    b6 = _bound6(merge.bound)
+    for s0 in range(0, P, chunk):
+        s1 = min(s0 + chunk, P)
+        p = pts[s0:s1]
+        cnt, offset, n, _ = _kf_pair_list(p, w, dep, K, H, W, intr, records)
+        count[s0:s1] = cnt
+        if n == 0:
+            continue
+        check(lib.dns_kf_pair_rows(ptr(records), n, ptr(p), s1 - s0, ptr(org), K, ptr(feat), Cc, h, w_, H, W, ptr(rel),
+                                   C.c_void_p(rows.data_ptr() + 4 * n_pe), ld, stream_ptr()), "dns_kf_pair_rows")
+        # Merge (models/decoder.py:67-77) on one view per row: OneBlob of the bound-normalised relative point into columns
+        # 0..n_pe of the rows the stem values already sit in, then the network; no concatenation
+        check(lib.dns_encode_fwd(ptr(rel), b6, n, merge.pe_fn.n_bins, None, None, None, ptr(rows), ld, None, 0, None, stream_ptr()),
+              "dns_encode_fwd")
+        lat = net(rows[:n])
+        check(lib.dns_kf_code_mean(ptr(lat), lat.stride(0), n, ptr(offset), ptr(cnt), s1 - s0, hidden,
+                                   C.c_void_p(code.data_ptr() + 4 * hidden * s0), stream_ptr()), "dns_kf_code_mean")
+    return code, count
+
+
 # ----------------------------------------------------------------------------- mesh components (csrc/mesh_cc.hip)
 def mesh_components(verts: torch.Tensor, faces: torch.Tensor):
     """verts [V,3] fp32, faces [F,3] int32 (any triangle list with shared vertex indices) -> (comp [F] int32: the smallest

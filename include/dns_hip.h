@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 18
+#define DNS_ABI_VERSION 19
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -797,6 +797,33 @@ int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t* faces, ui
 int dns_depth_l1(const float* a, const float* b, uint32_t V, uint32_t H, uint32_t W, double* partial, double* err, void* stream);
 int dns_views_see_any(const float* pts, uint32_t N, const float* w2c, uint32_t K, int H, int W, const float* intr, uint8_t* sees,
                       void* stream);
+
+/* ---- keyframe codes of the mesh vertex query (get_2d_feature, slams/meshing.py:311-377; csrc/mesh_feature.hip; ABI v19) -------
+ * For points pts [P,3] fp32 and K keyframes (w2c [K,16] fp32 row-major = torch.inverse(est_c2w), depth [K,H,W] fp32 = gt_depth,
+ * intr [host] (fx, fy, cx, cy)), keyframe k CONTRIBUTES to point p when it sees it -- dns_keyframe_project's projection and
+ * inequalities (0 < u < W, 0 < v < H, z < 0), no maximum-depth test -- and the truncation test passes at the rounded (half to
+ * even), clamped pixel (iu, iv): neither -z < depth[k, iv, iu] * 0.95 nor -z > depth[k, iv, iu] * 1.05 (fp32 products; both
+ * limits inclusive; a depth of 0 never passes).  The pairs form a list, point-major, keyframes ascending within a point:
+ *   dns_kf_pair_count: count [P] int32 = contributing keyframes per point.  P * K must stay below 2^31.
+ *   dns_kf_pair_emit: offset [P] int64 = the exclusive prefix of count (made by the caller); records [capacity, 4] int32,
+ *     16-byte aligned: pair offset[p] + i is {point, keyframe, iu, iv}.  Nothing is stored at or beyond `capacity`.
+ *   dns_kf_pair_rows: for the n records, rel [n,3] = pts[point] - origin[keyframe] (origin [K,3] = est_c2w[:3,3]; refer_p,
+ *     meshing.py:364) and, at code + pair * ld_code, the C values of the stem map feat [K,h,w,C] (channels last, half
+ *     resolution) up-sampled bilinearly to H x W with align_corners=True and read at (iv, iu) -- dns_feature_gather's tap
+ *     expressions.  C % 4 == 0, ld_code % 4 == 0, feat / code / records 16-byte aligned; anything else is DNS_E_ARG.
+ *   dns_kf_code_mean: code [P,D] = the sum of the point's segment of latents [n, ld_lat] (Merge's output per pair) added in list
+ *     order in fp32 -- the order of the reference's `+=` over the keyframes -- divided by (float)count; zeros where count == 0.
+ *     D % 4 == 0, ld_lat % 4 == 0, 16-byte aligned.
+ * No atomics: every output is the same bits for every call and for every split of the points into chunks. */
+int dns_kf_pair_count(const float* pts, uint32_t P, const float* w2c, uint32_t K, const float* depth, int H, int W,
+                      const float* intr, int32_t* count, void* stream);
+int dns_kf_pair_emit(const float* pts, uint32_t P, const float* w2c, uint32_t K, const float* depth, int H, int W,
+                     const float* intr, const int64_t* offset, int32_t* records, uint64_t capacity, void* stream);
+int dns_kf_pair_rows(const int32_t* records, uint64_t n, const float* pts, uint32_t P, const float* origin, uint32_t K,
+                     const float* feat, uint32_t C, int h, int w, int H, int W, float* rel, float* code, uint32_t ld_code,
+                     void* stream);
+int dns_kf_code_mean(const float* latents, uint32_t ld_lat, uint64_t n, const int64_t* offset, const int32_t* count, uint32_t P,
+                     uint32_t D, float* code, void* stream);
 
 #ifdef __cplusplus
 }
