@@ -13,6 +13,8 @@
 // Compiled with -ffp-contract=off (Makefile): the vertex positions are the float64 expression tests/mc_ref.py evaluates.
 #include <cmath>
 #include "common.hpp"
+#include "dev_project.hpp"
+#include "dev_reduce.hpp"
 #define MC_TABLE_SPACE __constant__
 #include "mc_table.hpp"
 
@@ -38,8 +40,6 @@ struct McWs {
   uint32_t* bcount;  // [n_blocks][2] vertices, triangles of 256 consecutive points
   uint64_t* bpre;    // [n_blocks][2] exclusive prefixes of bcount
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 McWs ws_layout(void* ws, uint32_t N) {
   const size_t n_chunks = (N + WAVE - 1) / WAVE, n_blocks = (N + MC_BLOCK - 1) / MC_BLOCK;
@@ -91,12 +91,6 @@ __device__ __forceinline__ McPoint load_point(const float* __restrict__ vol, con
   return q;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 __global__ __launch_bounds__(MC_BLOCK) void mc_count_kernel(const float* __restrict__ vol, McGrid g, float level, McWs ws) {
   __shared__ uint32_t s_v[MC_WAVES], s_t[MC_WAVES];
   const uint32_t p = blockIdx.x * MC_BLOCK + threadIdx.x;
@@ -131,27 +125,24 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_count_kernel(const float* __restr
 
 // One workgroup of 1024: thread t sums a contiguous run of blocks, an LDS scan of the 1024 run sums, then the run's prefixes.
 constexpr int SCAN_THREADS = 1024;
+struct McCounts {
+  uint64_t v, t;     // vertices, triangles
+  __device__ McCounts& operator+=(const McCounts& o) { return v += o.v, t += o.t, *this; }
+};
 __global__ __launch_bounds__(SCAN_THREADS) void mc_scan_kernel(McWs ws, uint32_t n_blocks, uint64_t* __restrict__ totals) {
-  __shared__ uint64_t s_v[SCAN_THREADS], s_t[SCAN_THREADS];
+  __shared__ McCounts s[SCAN_THREADS];
   const uint32_t t = threadIdx.x;
   const uint32_t per = (n_blocks + SCAN_THREADS - 1) / SCAN_THREADS;
   const uint32_t b0 = min(t * per, n_blocks), b1 = min(b0 + per, n_blocks);
-  uint64_t sv = 0, st = 0;
-  for (uint32_t b = b0; b < b1; ++b) sv += ws.bcount[2 * b], st += ws.bcount[2 * b + 1];
-  s_v[t] = sv, s_t[t] = st;
-  __syncthreads();
-  for (uint32_t o = 1; o < SCAN_THREADS; o <<= 1) {            // Hillis-Steele inclusive scan
-    const uint64_t av = t >= o ? s_v[t - o] : 0, at = t >= o ? s_t[t - o] : 0;
-    __syncthreads();
-    s_v[t] += av, s_t[t] += at;
-    __syncthreads();
-  }
-  uint64_t pv = s_v[t] - sv, pt = s_t[t] - st;
+  McCounts own{0, 0};
+  for (uint32_t b = b0; b < b1; ++b) own.v += ws.bcount[2 * b], own.t += ws.bcount[2 * b + 1];
+  const McCounts incl = block_scan_inclusive<SCAN_THREADS>(s, own);
+  uint64_t pv = incl.v - own.v, pt = incl.t - own.t;
   for (uint32_t b = b0; b < b1; ++b) {
     ws.bpre[2 * b] = pv, ws.bpre[2 * b + 1] = pt;
     pv += ws.bcount[2 * b], pt += ws.bcount[2 * b + 1];
   }
-  if (t == SCAN_THREADS - 1) totals[0] = s_v[t], totals[1] = s_t[t];
+  if (t == SCAN_THREADS - 1) totals[0] = incl.v, totals[1] = incl.t;
 }
 
 // rank of grid edge (q, axis) among the crossing edges = its vertex index
@@ -244,8 +235,7 @@ __global__ __launch_bounds__(KF_BLOCK) void kf_project_kernel(const float* __res
   __shared__ float s_d[KF_TILE];
   const uint32_t p = blockIdx.x * KF_BLOCK + threadIdx.x;
   const bool live = p < P;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (live) px = pts[3 * (size_t)p], py = pts[3 * (size_t)p + 1], pz = pts[3 * (size_t)p + 2];
+  const float3 pt = load_point3(pts, p, live);
   bool found = false, seen = false;
   float lab = 0.f;
   const float fW = (float)W, fH = (float)H;
@@ -253,26 +243,19 @@ __global__ __launch_bounds__(KF_BLOCK) void kf_project_kernel(const float* __res
   for (int hi = (int)K; hi > 0; hi -= KF_TILE) {
     const int lo = max(hi - KF_TILE, 0), n = hi - lo;
     __syncthreads();
-    for (int x = threadIdx.x; x < n * 12; x += KF_BLOCK) s_w[x] = w2c[(size_t)(lo + x / 12) * 16 + x % 12];
+    stage_poses<KF_BLOCK>(s_w, w2c, (uint32_t)lo, n);
     for (int x = threadIdx.x; x < n; x += KF_BLOCK) s_d[x] = max_depth[lo + x] * 1.2f;
     __syncthreads();
     if (live && !(found && seen)) {
       for (int kk = n - 1; kk >= 0; --kk) {
-        const float* m = s_w + kk * 12;
-        // w2c @ [p, 1], x *= -1, K @ cam, z + 1e-8, uv / z (meshing.py:319-329, 210-220)
-        const float cxw = m[0] * px + m[1] * py + m[2] * pz + m[3];
-        const float cyw = m[4] * px + m[5] * py + m[6] * pz + m[7];
-        const float czw = m[8] * px + m[9] * py + m[10] * pz + m[11];
-        const float z = czw + 1e-8f;
-        const float u = (fx * -cxw + cx * czw) / z;
-        const float v = (fy * cyw + cy * czw) / z;
-        if (!(u < fW && u > 0.f && v < fH && v > 0.f && z < 0.f)) continue;
+        const Projected q = project(s_w + kk * 12, pt, fx, fy, cx, cy, PROJ_EPS_MESHING);      // the meshing convention
+        if (!inside_meshing(q, fW, fH)) continue;
         if (!found) {
           found = true;
-          const int iu = min(max((int)rintf(u), 0), W - 1), iv = min(max((int)rintf(v), 0), H - 1);
+          const int iu = round_pixel(q.u, W), iv = round_pixel(q.v, H);
           lab = labels[((size_t)(lo + kk) * H + iv) * W + iu];
         }
-        if (-czw < s_d[kk]) seen = true;
+        if (-q.czw < s_d[kk]) seen = true;
         if (seen) break;
       }
     }

@@ -23,6 +23,7 @@
 // A vertex index outside [0, V) is never dereferenced: it sets status[1] and the face contributes no edge and no area.
 // Compiled with -ffp-contract=off (Makefile): the area is the float64 expression tests/mesh_cc_ref.py evaluates.
 #include "common.hpp"
+#include "dev_reduce.hpp"
 
 namespace dns {
 
@@ -43,8 +44,6 @@ struct CcWs {
   int32_t* parent;   // [F]
   uint32_t cap;      // 4 F
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 CcWs ws_layout(void* ws, uint32_t F) {
   CcWs w;
@@ -140,12 +139,6 @@ __global__ __launch_bounds__(CC_BLOCK) void cc_union_kernel(CcWs ws) {
     if (old == hi) return;
     a = old, b = lo;                                             // hi was hooked meanwhile: old < hi is its parent
   }
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
 }
 
 __global__ __launch_bounds__(CC_FLAT_BLOCK) void cc_flatten_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,

@@ -33,6 +33,8 @@
 // LDS tiles, a workgroup leaves at the first tile after which all its points are seen.
 #include <algorithm>
 #include "common.hpp"
+#include "dev_project.hpp"
+#include "dev_reduce.hpp"
 
 namespace dns {
 
@@ -68,8 +70,6 @@ struct NnWs {
   uint64_t* best;        // [N]
   uint32_t target, cells_alloc;
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 inline uint32_t cells_target(uint32_t M) {
   const uint64_t t = 2ull * M;
@@ -242,8 +242,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_scan_sums_kernel(NnWs w) {
   uint32_t v = 0;
 #pragma unroll
   for (int k = 0; k < NN_SCAN_PER; ++k) v += w.count[base + k];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum(v);
   if (threadIdx.x % WAVE == 0) s[threadIdx.x / WAVE] = v;
   __syncthreads();
   if (threadIdx.x == 0) w.sums[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
@@ -253,15 +252,8 @@ __global__ __launch_bounds__(NN_SUMS_BLOCK) void nn_scan_top_kernel(NnWs w, uint
   __shared__ uint32_t s[NN_SUMS_BLOCK];
   const uint32_t t = threadIdx.x;
   const uint32_t own = t < n_blocks ? w.sums[t] : 0u;
-  s[t] = own;
-  __syncthreads();
-  for (uint32_t o = 1; o < NN_SUMS_BLOCK; o <<= 1) {
-    const uint32_t a = t >= o ? s[t - o] : 0u;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  if (t < n_blocks) w.sums[t] = s[t] - own;
+  const uint32_t incl = block_scan_inclusive<NN_SUMS_BLOCK>(s, own);
+  if (t < n_blocks) w.sums[t] = incl - own;
 }
 
 __global__ __launch_bounds__(NN_BLOCK) void nn_scan_local_kernel(NnWs w, uint32_t M) {
@@ -270,15 +262,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_scan_local_kernel(NnWs w, uint32_
   uint32_t c[NN_SCAN_PER], own = 0;
 #pragma unroll
   for (int k = 0; k < NN_SCAN_PER; ++k) c[k] = w.count[base + k], own += c[k];
-  s[t] = own;
-  __syncthreads();
-  for (uint32_t o = 1; o < NN_BLOCK; o <<= 1) {
-    const uint32_t a = t >= o ? s[t - o] : 0u;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  uint32_t run = w.sums[blockIdx.x] + s[t] - own;
+  uint32_t run = w.sums[blockIdx.x] + block_scan_inclusive<NN_BLOCK>(s, own) - own;
 #pragma unroll
   for (int k = 0; k < NN_SCAN_PER; ++k) {
     w.start[base + k] = run;
@@ -502,9 +486,7 @@ __global__ __launch_bounds__(NN_BLOCK) void icp_reduce_kernel(NnWs w, const floa
     }
   }
 #pragma unroll
-  for (int k = 0; k < ICP_SUMS; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o);
+  for (int k = 0; k < ICP_SUMS; ++k) a[k] = wave_sum(a[k]);
   if (threadIdx.x % WAVE == 0)
 #pragma unroll
     for (int k = 0; k < ICP_SUMS; ++k) s_w[threadIdx.x / WAVE][k] = a[k];
@@ -567,8 +549,7 @@ __global__ __launch_bounds__(NN_BLOCK) void icp_solve_kernel(const double* __res
   for (int k = 0; k < ICP_SUMS; ++k) {
     a[k] = 0.0;
     for (uint32_t r = threadIdx.x; r < n_rows; r += NN_BLOCK) a[k] += partial[(size_t)r * ICP_SUMS + k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o);
+    a[k] = wave_sum(a[k]);
   }
   if (threadIdx.x % WAVE == 0)
 #pragma unroll
@@ -651,25 +632,16 @@ __global__ __launch_bounds__(FR_BLOCK) void frustum_seen_kernel(const float* __r
   __shared__ float s_w[FR_TILE * 12];
   const uint32_t p = blockIdx.x * FR_BLOCK + threadIdx.x;
   const bool live = p < P;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (live) px = pts[3 * (size_t)p], py = pts[3 * (size_t)p + 1], pz = pts[3 * (size_t)p + 2];
+  const float3 pt = load_point3(pts, p, live);
   bool seen = false;
   for (uint32_t lo = 0; lo < K; lo += FR_TILE) {
     const int n = (int)min((uint32_t)FR_TILE, K - lo);
     __syncthreads();
-    for (int x = threadIdx.x; x < n * 12; x += FR_BLOCK) s_w[x] = w2c[(size_t)(lo + x / 12) * 16 + x % 12];
+    stage_poses<FR_BLOCK>(s_w, w2c, lo, n);
     __syncthreads();
     if (live && !seen) {
       for (int kk = 0; kk < n; ++kk) {
-        const float* m = s_w + kk * 12;
-        // w2c @ [p, 1], x *= -1, K @ cam, z + 1e-5, uv / z (eval_3d.py:78-87)
-        const float cxw = m[0] * px + m[1] * py + m[2] * pz + m[3];
-        const float cyw = m[4] * px + m[5] * py + m[6] * pz + m[7];
-        const float czw = m[8] * px + m[9] * py + m[10] * pz + m[11];
-        const float z = czw + 1e-5f;
-        const float u = (fx * -cxw + cx * czw) / z;
-        const float v = (fy * cyw + cy * czw) / z;
-        if (0.f <= -z && u < fW && u > 0.f && v < fH && v > 0.f) {
+        if (inside_eval(project(s_w + kk * 12, pt, fx, fy, cx, cy, PROJ_EPS_EVAL), fW, fH)) {      // the evaluation convention
           seen = true;
           break;
         }

@@ -9,6 +9,7 @@
 // the caller), and the per-point mean.  No atomics anywhere: a point's latents are added in list order, which is the
 // reference's keyframe order, so every result is the same bits from call to call and for every chunking by points.
 #include "common.hpp"
+#include "dev_project.hpp"
 
 namespace dns {
 
@@ -17,9 +18,8 @@ namespace {
 constexpr int KFP_BLOCK = 256;
 constexpr int KFP_TILE = 256;   // keyframes staged in LDS at a time (12 KB), as kf_project_kernel (mesh.hip) does
 
-// One thread per point, keyframes in ASCENDING order.  The projection and the seen test are kf_project_kernel's source
-// expressions (mesh.hip; this file is compiled without contraction like that one), without its maximum-depth test, so labels
-// and codes agree on which keyframes see a point.  EMIT = false: count[p] = number of contributing keyframes.  EMIT = true:
+// One thread per point, keyframes in ASCENDING order.  The meshing convention of dev_project.hpp, as kf_project_kernel (mesh.hip)
+// without its maximum-depth test: labels and codes agree on which keyframes see a point.  EMIT = false: count[p] = number of contributing keyframes.  EMIT = true:
 // record i of point p goes to rec[offset[p] + i] = {p, keyframe, iu, iv}; nothing is stored at or beyond cap.
 template <bool EMIT>
 __global__ __launch_bounds__(KFP_BLOCK) void kf_pair_kernel(const float* __restrict__ pts, uint32_t P, const float* __restrict__ w2c,
@@ -30,8 +30,7 @@ __global__ __launch_bounds__(KFP_BLOCK) void kf_pair_kernel(const float* __restr
   __shared__ float s_w[KFP_TILE * 12];
   const uint32_t p = blockIdx.x * KFP_BLOCK + threadIdx.x;
   const bool live = p < P;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (live) px = pts[3 * (size_t)p], py = pts[3 * (size_t)p + 1], pz = pts[3 * (size_t)p + 2];
+  const float3 pt = load_point3(pts, p, live);
   const float fW = (float)W, fH = (float)H;
   uint32_t n_pairs = 0;
   uint64_t base = 0;
@@ -39,22 +38,15 @@ __global__ __launch_bounds__(KFP_BLOCK) void kf_pair_kernel(const float* __restr
   for (uint32_t lo = 0; lo < K; lo += KFP_TILE) {
     const int n = (int)min((uint32_t)KFP_TILE, K - lo);
     __syncthreads();
-    for (int x = threadIdx.x; x < n * 12; x += KFP_BLOCK) s_w[x] = w2c[(size_t)(lo + x / 12) * 16 + x % 12];
+    stage_poses<KFP_BLOCK>(s_w, w2c, lo, n);
     __syncthreads();
     if (!live) continue;
     for (int kk = 0; kk < n; ++kk) {
-      const float* m = s_w + kk * 12;
-      // w2c @ [p, 1], x *= -1, K @ cam, z + 1e-8, uv / z (meshing.py:323-335)
-      const float cxw = m[0] * px + m[1] * py + m[2] * pz + m[3];
-      const float cyw = m[4] * px + m[5] * py + m[6] * pz + m[7];
-      const float czw = m[8] * px + m[9] * py + m[10] * pz + m[11];
-      const float z = czw + 1e-8f;
-      const float u = (fx * -cxw + cx * czw) / z;
-      const float v = (fy * cyw + cy * czw) / z;
-      if (!(u < fW && u > 0.f && v < fH && v > 0.f && z < 0.f)) continue;
-      const int iu = min(max((int)rintf(u), 0), W - 1), iv = min(max((int)rintf(v), 0), H - 1);
+      const Projected q = project(s_w + kk * 12, pt, fx, fy, cx, cy, PROJ_EPS_MESHING);
+      if (!inside_meshing(q, fW, fH)) continue;
+      const int iu = round_pixel(q.u, W), iv = round_pixel(q.v, H);
       const float d = depth[((size_t)(lo + kk) * H + iv) * W + iu];
-      const float dp = -z;
+      const float dp = -q.z;
       // trunc = (1 - front) (1 - back), meshing.py:352-356; a depth hole (d = 0) is behind the surface: dp > 0
       if (dp < d * 0.95f || dp > d * 1.05f) continue;
       if (EMIT) {

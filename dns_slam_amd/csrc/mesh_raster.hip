@@ -34,9 +34,11 @@
 // dns_depth_l1: err[v] = sum |a - b| / (H W) over all pixels in float64: DNS_DEPTH_L1_PARTS workgroups per view, each a strided
 // sum, a butterfly over the wave and the waves in order; then one thread per view adds the parts in order.  No atomics.
 //
-// dns_views_see_any: frustum_seen_kernel's projection (mesh_eval.hip) with the roles turned round: one flag per pose.
+// dns_views_see_any: frustum_seen_kernel (mesh_eval.hip) with the roles turned round, one flag per pose (dev_project.hpp).
 #include <algorithm>
 #include "common.hpp"
+#include "dev_project.hpp"
+#include "dev_reduce.hpp"
 
 namespace dns {
 
@@ -228,8 +230,7 @@ __global__ __launch_bounds__(L1_BLOCK) void l1_partial_kernel(const float* __res
   double s = 0.0;
   for (uint64_t p = (uint64_t)part * L1_BLOCK + threadIdx.x; p < n_pix; p += (uint64_t)DNS_DEPTH_L1_PARTS * L1_BLOCK)
     s += fabs((double)pa[p] - (double)pb[p]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (threadIdx.x % WAVE == 0) s_w[threadIdx.x / WAVE] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -263,26 +264,16 @@ __global__ __launch_bounds__(VS_BLOCK) void views_see_any_kernel(const float* __
   __shared__ uint32_t s_hit[VS_TILE];
   const uint32_t p = blockIdx.x * VS_BLOCK + threadIdx.x;
   const bool live = p < N;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (live) px = pts[3 * (size_t)p], py = pts[3 * (size_t)p + 1], pz = pts[3 * (size_t)p + 2];
+  const float3 pt = load_point3(pts, p, live);
   for (uint32_t lo = 0; lo < K; lo += VS_TILE) {
     const int n = (int)min((uint32_t)VS_TILE, K - lo);
     __syncthreads();
-    for (int x = threadIdx.x; x < n * 12; x += VS_BLOCK) s_w[x] = w2c[(size_t)(lo + x / 12) * 16 + x % 12];
+    stage_poses<VS_BLOCK>(s_w, w2c, lo, n);
     if (threadIdx.x < VS_TILE) s_hit[threadIdx.x] = 0u;
     __syncthreads();
     if (live) {
-      for (int kk = 0; kk < n; ++kk) {
-        const float* m = s_w + kk * 12;
-        // the expressions of frustum_seen_kernel, unchanged
-        const float cxw = m[0] * px + m[1] * py + m[2] * pz + m[3];
-        const float cyw = m[4] * px + m[5] * py + m[6] * pz + m[7];
-        const float czw = m[8] * px + m[9] * py + m[10] * pz + m[11];
-        const float z = czw + 1e-5f;
-        const float u = (fx * -cxw + cx * czw) / z;
-        const float v = (fy * cyw + cy * czw) / z;
-        if (0.f <= -z && u < fW && u > 0.f && v < fH && v > 0.f) s_hit[kk] = 1u;     // every writer stores the same value
-      }
+      for (int kk = 0; kk < n; ++kk)                              // the evaluation convention; every writer stores the same value
+        if (inside_eval(project(s_w + kk * 12, pt, fx, fy, cx, cy, PROJ_EPS_EVAL), fW, fH)) s_hit[kk] = 1u;
     }
     __syncthreads();
     if ((int)threadIdx.x < n && s_hit[threadIdx.x]) sees[lo + threadIdx.x] = 1;     // likewise across workgroups
@@ -297,8 +288,6 @@ using namespace dns;
 
 namespace {
 
-inline size_t rs_align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 inline uint64_t rs_list_entries(uint32_t F, uint32_t V, uint32_t cap) {
   return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)F * V, cap));
 }
@@ -307,7 +296,7 @@ inline uint64_t rs_list_entries(uint32_t F, uint32_t V, uint32_t cap) {
 
 extern "C" uint64_t dns_rasterize_ws_bytes(uint32_t F, uint32_t V, uint32_t H, uint32_t W) {
   if (F >= (1u << 31) || H == 0 || W == 0 || H > 32768u || W > 32768u) return 0;
-  return rs_align256((size_t)RS_MAX_LAUNCHES * 4) + rs_align256(rs_list_entries(F, V, RS_LIST_CAP) * 8);
+  return align256((size_t)RS_MAX_LAUNCHES * 4) + align256(rs_list_entries(F, V, RS_LIST_CAP) * 8);
 }
 
 extern "C" int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t* faces, uint32_t F, const float* w2c, uint32_t V,
@@ -332,7 +321,7 @@ extern "C" int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t
               list_cap, F, V, (unsigned long long)n_launch, RS_MAX_LAUNCHES);
   hipStream_t st = (hipStream_t)stream;
   uint32_t* counters = (uint32_t*)ws;
-  uint64_t* list = (uint64_t*)((char*)ws + rs_align256((size_t)RS_MAX_LAUNCHES * 4));
+  uint64_t* list = (uint64_t*)((char*)ws + align256((size_t)RS_MAX_LAUNCHES * 4));
   uint32_t* img = (uint32_t*)depth;
   const size_t n_words = (size_t)V * H * W;
   const RsCam cam = {intr[0], intr[1], intr[2], intr[3], z_near, z_far, (int)H, (int)W};

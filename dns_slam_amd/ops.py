@@ -934,20 +934,32 @@ def marching_cubes(volume: torch.Tensor, level: float, origin, spacing):
     return verts, faces
 
 
+def _pose_args(who, points, w2c):
+    """points [P,3] and w2c [K,4,4] as the pose kernels take them -> (pts, w, K): detached contiguous fp32 CUDA tensors."""
+    pts = points.detach().contiguous().float()
+    w = w2c.detach().contiguous().float()            # torch.inverse of a batch returns column-major matrices
+    require_cuda(pts, w)
+    if pts.dim() != 2 or pts.shape[1] != 3 or w.dim() != 3 or w.shape[1:] != (4, 4):
+        raise ValueError(f"{who}: points [P,3] and w2c [K,4,4], got {tuple(pts.shape)} and {tuple(w.shape)}")
+    return pts, w, int(w.shape[0])
+
+
+def _intrinsics(fx, fy, cx, cy):
+    return (C.c_float * 4)(float(fx), float(fy), float(cx), float(cy))
+
+
 def keyframe_project(points: torch.Tensor, w2c: torch.Tensor, labels: torch.Tensor, max_depth: torch.Tensor, cam: dict):
     """points [P,3] world, w2c [K,4,4] (torch.inverse(est_c2w) in fp32), labels [K,H,W] (gt_label), max_depth [K] (max of each
     keyframe's gt_depth), cam {'fx','fy','cx','cy'} -> (label [P] fp32: get_2d_feature's label_pts, meshing.py:313-373;
     seen [P] bool: point_masks' seen mask without the depth test, meshing.py:203-274)."""
-    pts = points.detach().contiguous().float()
-    w = w2c.detach().contiguous().float()            # torch.inverse of a batch returns column-major matrices
+    pts, w, K = _pose_args("keyframe_project", points, w2c)
     lab = labels.detach().contiguous().float()
     md = max_depth.detach().contiguous().float().reshape(-1)
-    require_cuda(pts, w, lab, md)
-    K = int(w.shape[0])
-    if w.shape[1:] != (4, 4) or lab.dim() != 3 or lab.shape[0] != K or md.numel() != K:
+    require_cuda(lab, md)
+    if lab.dim() != 3 or lab.shape[0] != K or md.numel() != K:
         raise ValueError("keyframe_project: w2c [K,4,4], labels [K,H,W], max_depth [K]")
     H, W = int(lab.shape[1]), int(lab.shape[2])
-    intr = (C.c_float * 4)(float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]))
+    intr = _intrinsics(cam["fx"], cam["fy"], cam["cx"], cam["cy"])
     P = pts.shape[0]
     label = torch.empty(P, device=pts.device)
     seen = torch.empty(P, dtype=torch.uint8, device=pts.device)
@@ -966,22 +978,18 @@ def _kf_args(who, points, w2c, depths, cam, chunked=False):
             raise ValueError(f"{who}: dns_slam_amd ops run on the GPU only (got a non-CUDA tensor); there is no CPU fallback")
     if len({t.device for t in (points, w2c, depths)}) != 1:
         raise ValueError(f"{who}: the arguments live on different devices")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"{who}: points must be [P,3], got {tuple(points.shape)}")
-    if w2c.dim() != 3 or w2c.shape[1:] != (4, 4) or depths.dim() != 3 or depths.shape[0] != w2c.shape[0]:
+    pts, w, K = _pose_args(who, points, w2c)
+    if depths.dim() != 3 or depths.shape[0] != K:
         raise ValueError(f"{who}: w2c [K,4,4] and depths [K,H,W] with one K, got {tuple(w2c.shape)} and {tuple(depths.shape)}")
     if not all(t.is_floating_point() for t in (points, w2c, depths)):
         raise ValueError(f"{who}: points, w2c and depths must be floating point")
-    pts = points.detach().contiguous().float()
-    w = w2c.detach().contiguous().float()
     dep = depths.detach().contiguous().float()
-    K, H, W = int(w.shape[0]), int(dep.shape[1]), int(dep.shape[2])
+    H, W = int(dep.shape[1]), int(dep.shape[2])
     if H < 1 or W < 1:
         raise ValueError(f"{who}: depth images of {H} x {W}")
     if not chunked and pts.shape[0] * max(K, 1) >= 1 << 31:           # (keyframe_codes launches per chunk: chunk * K is bounded there)
         raise ValueError(f"{who}: {pts.shape[0]} points x {K} keyframes (must be < 2^31 pairs)")
-    intr = (C.c_float * 4)(float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]))
-    return pts, w, dep, K, H, W, intr
+    return pts, w, dep, K, H, W, _intrinsics(cam["fx"], cam["fy"], cam["cx"], cam["cy"])
 
 
 def _kf_pair_list(pts, w, dep, K, H, W, intr, records=None):
@@ -1248,13 +1256,8 @@ def frustum_seen(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: fl
     """points [P,3] fp32 world, w2c [K,4,4] fp32 world->camera -> seen [P] bool: some pose sees the point under check_proj of
     eval_3d.py:62-88 (cull_mesh.py:53-74) in fp32: x = -cam.x, z' = cam.z + 1e-5, u = (fx x + cx cam.z) / z', v = (fy cam.y +
     cy cam.z) / z'; seen iff -z' >= 0, 0 < u < W, 0 < v < H.  K = 0 sees nothing."""
-    pts = points.detach().contiguous().float()
-    w = w2c.detach().contiguous().float()
-    require_cuda(pts, w)
-    if pts.dim() != 2 or pts.shape[1] != 3 or w.dim() != 3 or w.shape[1:] != (4, 4):
-        raise ValueError(f"frustum_seen: points [P,3] and w2c [K,4,4], got {tuple(pts.shape)} and {tuple(w.shape)}")
-    P, K = int(pts.shape[0]), int(w.shape[0])
-    intr = (C.c_float * 4)(float(fx), float(fy), float(cx), float(cy))
+    pts, w, K = _pose_args("frustum_seen", points, w2c)
+    P, intr = int(pts.shape[0]), _intrinsics(fx, fy, cx, cy)
     seen = torch.empty(P, dtype=torch.uint8, device=pts.device)
     check(lib.dns_frustum_seen(ptr(pts), P, ptr(w), K, int(H), int(W), intr, ptr(seen), stream_ptr()), "dns_frustum_seen")
     return seen.bool()
@@ -1410,13 +1413,11 @@ RASTER_METHODS = ("auto", "simple")
 def _raster_arguments(verts, faces, w2c, H, W, method):
     if not all(isinstance(t, torch.Tensor) for t in (verts, faces, w2c)):
         raise ValueError("rasterize_depth: verts, faces and w2c must be tensors")
-    v = verts.detach().contiguous().float()
+    v, w, _ = _pose_args("rasterize_depth", verts, w2c)
     f = faces.detach().contiguous()
-    w = w2c.detach().contiguous().float()
-    require_cuda(v, f, w)
-    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or w.dim() != 3 or w.shape[1:] != (4, 4):
-        raise ValueError(f"rasterize_depth: verts [P,3], faces [F,3] and w2c [V,4,4], got {tuple(v.shape)}, {tuple(f.shape)} and "
-                         f"{tuple(w.shape)}")
+    require_cuda(f)
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"rasterize_depth: faces [F,3], got {tuple(f.shape)}")
     if f.dtype not in (torch.int32, torch.int64):
         raise ValueError(f"rasterize_depth: faces must be int32 or int64, got {f.dtype}")
     if method not in RASTER_METHODS:
@@ -1456,9 +1457,8 @@ def rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near=0.01,
     if ws_b == 0:
         raise ValueError(f"rasterize_depth: {F} faces at {H} x {W} are refused (F >= 2^31)")
     ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
-    intr = (C.c_float * 4)(float(fx), float(fy), float(cx), float(cy))
     flags = (1 if method == "simple" else 0) | (2 if stats else 0)
-    check(lib.dns_rasterize_depth(ptr(v), P, ptr(f), F, ptr(w), V, int(H), int(W), intr, zn, zf, flags, int(list_cap), ptr(ws),
+    check(lib.dns_rasterize_depth(ptr(v), P, ptr(f), F, ptr(w), V, int(H), int(W), _intrinsics(fx, fy, cx, cy), zn, zf, flags, int(list_cap), ptr(ws),
                                   ptr(depth), ptr(status), stream_ptr()), "dns_rasterize_depth")
     return depth, status
 
@@ -1509,13 +1509,8 @@ def views_see_any(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: f
     this per pose).  No host read."""
     if not isinstance(points, torch.Tensor) or not isinstance(w2c, torch.Tensor):
         raise ValueError("views_see_any: points and w2c must be tensors")
-    pts = points.detach().contiguous().float()
-    w = w2c.detach().contiguous().float()
-    require_cuda(pts, w)
-    if pts.dim() != 2 or pts.shape[1] != 3 or w.dim() != 3 or w.shape[1:] != (4, 4):
-        raise ValueError(f"views_see_any: points [N,3] and w2c [K,4,4], got {tuple(pts.shape)} and {tuple(w.shape)}")
-    N, K = int(pts.shape[0]), int(w.shape[0])
-    intr = (C.c_float * 4)(float(fx), float(fy), float(cx), float(cy))
+    pts, w, K = _pose_args("views_see_any", points, w2c)
     sees = torch.empty(K, dtype=torch.uint8, device=w.device)
-    check(lib.dns_views_see_any(ptr(pts), N, ptr(w), K, int(H), int(W), intr, ptr(sees), stream_ptr()), "dns_views_see_any")
+    check(lib.dns_views_see_any(ptr(pts), int(pts.shape[0]), ptr(w), K, int(H), int(W), _intrinsics(fx, fy, cx, cy), ptr(sees),
+                                stream_ptr()), "dns_views_see_any")
     return sees.bool()

@@ -5,9 +5,11 @@
 // ascending keyframes and never on a depth hole, the bilinear value against float64, C = 6 refused, the mean bit-equal to the
 // ordered sum.  No GPU is involved.  From the repository root:
 //
-//   sed -e 's/#include "common.hpp"//' -e 's/extern "C" //' dns_slam_amd/csrc/mesh_feature.hip > /tmp/kf_kernels.inc
+//   mkdir -p /tmp/kf_check && for f in dev_project.hpp mesh_feature.hip; do \
+//     sed -e 's/#include "common.hpp"//' -e 's/extern "C" //' dns_slam_amd/csrc/$f > /tmp/kf_check/$f; done
 //   g++ -std=c++20 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread \
-//       -Wno-unused-value -I/tmp tools/kf_host_check.cpp -o /tmp/kf_host_check && /tmp/kf_host_check
+//       -Wno-unused-value -I/tmp/kf_check tools/kf_host_check.cpp -o /tmp/kf_check/kf_host_check && /tmp/kf_check/kf_host_check
+// (dev_project.hpp is taken from the source tree the same way as the kernels: only its include of the HIP headers is dropped.)
 #include <algorithm>
 #include <barrier>
 #include <cmath>
@@ -20,6 +22,8 @@
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
 struct int4 { int x, y, z, w; };
 struct alignas(16) float4 { float x, y, z, w; };
+struct float3 { float x, y, z; };
+inline float3 make_float3(float a, float b, float c) { return {a, b, c}; }
 inline int4 make_int4(int a, int b, int c, int d) { return {a, b, c, d}; }
 inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
 inline thread_local dim3 threadIdx, blockIdx;
@@ -28,6 +32,8 @@ inline void __syncthreads() { g_bar->arrive_and_wait(); }
 inline float __fmul_rn(float a, float b) { return a * b; }
 using std::max; using std::min;
 #define __global__
+#define __device__
+#define __forceinline__ inline
 #define __restrict__
 #define __launch_bounds__(x)
 #define __shared__ static
@@ -49,7 +55,7 @@ void launch(F kern, dim3 grid, dim3 block, A... args) {
 }
 #define DNS_LAUNCH(kern, grid, block, lds, st, ...) launch(kern, grid, block, __VA_ARGS__)
 
-#include "kf_kernels.inc"
+#include "mesh_feature.hip"
 #include <random>
 int main() {
   std::mt19937 g(1);
