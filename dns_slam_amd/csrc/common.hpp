@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/dns_hip.h"
+#include "grid_levels.hpp"
 
 namespace dns {
 
@@ -68,30 +69,6 @@ struct KernelSpan {
 // maximum supplied, i.e. without its memset, and goes wrong with it).
 int fill_words(void* dst, uint32_t value, size_t n_words, hipStream_t st, const char* who);
 int fill_words2(void* a, uint32_t va, size_t na, void* b, uint32_t vb, size_t nb, hipStream_t st, const char* who);
-constexpr int MAX_DYN_LDS = 160 * 1024;      // gfx950: 160 KiB of LDS per CU, all of it available to one workgroup
-
-// Device-side copy of the level table, passed by value as a kernel argument.
-struct GridLevels {
-  uint32_t n_levels;
-  float scale[DNS_MAX_LEVELS];
-  uint32_t resolution[DNS_MAX_LEVELS];
-  uint32_t size[DNS_MAX_LEVELS];
-  uint32_t offset[DNS_MAX_LEVELS];
-  uint32_t hashed[DNS_MAX_LEVELS];
-};
-
-inline GridLevels to_levels(const DnsGridMeta* m) {
-  GridLevels g;
-  g.n_levels = m->n_levels;
-  for (uint32_t l = 0; l < DNS_MAX_LEVELS; ++l) {
-    g.scale[l] = m->scale[l];
-    g.resolution[l] = m->resolution[l];
-    g.size[l] = m->size[l];
-    g.offset[l] = m->offset[l];
-    g.hashed[l] = m->hashed[l];
-  }
-  return g;
-}
 
 namespace sp { struct XsIn; }                // split-row input of the MLP kernels (mlp_split.hpp); NULL = fp32 rows
 // split-operand MLP kernels (mlp_split.hip); arguments validated by the C-ABI wrappers in mlp.hip
@@ -114,5 +91,10 @@ uint32_t mlp_prepared_fwd_bytes(uint32_t n_in, uint32_t n_out, uint32_t nn, uint
 uint32_t mlp_prepared_bytes(uint32_t n_in, uint32_t n_out, uint32_t nn, uint32_t nl);
 int launch_mlp_prepare(const float* params, uint32_t param_stride, uint32_t n_in, uint32_t n_out, uint32_t nn, uint32_t nl,
                        uint32_t n_sets, unsigned char* blob, hipStream_t st, uint32_t n_in_w = 0);
+// table-gradient scatter of dns_encode_bwd (scatter.hip): the launches of a plan built by scatter_plan() (scatter_plan.hpp) over the
+// workspace `ws` that plan sized; x, d_grid, alignment and the plan's LDS limits are checked by the caller
+struct ScatterPlan;
+int launch_table_scatter(const float* x, uint32_t P, const GridLevels& lv, const float* d_grid, uint32_t ld_dgrid, float* d_table,
+                         float* ws, const ScatterPlan& plan, hipStream_t st);
 
 }  // namespace dns

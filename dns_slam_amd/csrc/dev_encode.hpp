@@ -1,4 +1,4 @@
-// Device helpers of the point-encoding kernels (encode.hip): hash / dense row index, the OneBlob kernel integrals and the fp64
+// Device helpers of the point-encoding kernels (encode.hip; the table scatter of scatter.hip needs none of them): hash / dense row index, the OneBlob kernel integrals and the fp64
 // normalisation of a point -- shared with the fused tracker iteration (track_fused.inc).  encode.hip is compiled with
 // -ffp-contract=off (value-exact arithmetic shared with oracle/tcnn_ref.py); the functions whose results a contraction would change
 // carry the same setting as a function-level pragma, so they give the same bits in every translation unit.

@@ -55,7 +55,7 @@ class _TimedLib:
     @staticmethod
     def _grid_info(meta_ref):
         """levels of a grid and how many of them the scatter sends through pair lists (hashed levels of more than one 8192-row
-        chunk, dense levels of at least six: csrc/encode.hip list_plan)"""
+        chunk, dense levels of at least six: csrc/scatter_plan.hpp list_plan)"""
         m = getattr(meta_ref, "_obj", None)
         if m is None:
             return None
