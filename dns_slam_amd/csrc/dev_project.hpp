@@ -1,10 +1,12 @@
 // "Does pose k see point p": the pose tile and the pinhole projection of kf_project_kernel (mesh.hip), kf_pair_kernel
-// (mesh_feature.hip), frustum_seen_kernel (mesh_eval.hip) and views_see_any_kernel (mesh_raster.hip).  Their agreement is part of
+// (mesh_feature.hip), frustum_seen_kernel (mesh_eval.hip), views_see_any_kernel (mesh_raster.hip) and the point-mask kernels
+// (mesh_masks.hip).  Their agreement is part of
 // the result (labels and codes pick the same keyframes; views_see_any is frustum_seen per pose), so the expressions exist here
 // and nowhere else.  Each kernel keeps its own loop over the tiles, its tile size and its exits.
 // project(): cam = w2c @ [p, 1], x *= -1, K @ cam, z = cam.z + eps, (u, v) = uv / z, in fp32.  Two conventions:
 //   meshing     (get_2d_feature / point_masks, reference slams/meshing.py:319-335 and 210-220): eps = 1e-8;
-//               inside iff u < W, u > 0, v < H, v > 0, z < 0; the pixel read is round-half-even(u, v) clamped to the image.
+//               inside iff u < W, u > 0, v < H, v > 0, z < 0; the pixel read is round-half-even(u, v) clamped to the image;
+//               point_masks' forecast frustum: the same with the image widened by 1000 px on every side.
 //   evaluation  (check_proj, reference eval_3d.py:78-87 / cull_mesh.py:53-74): eps = 1e-5;
 //               inside iff 0 <= -z, u < W, u > 0, v < H, v > 0.
 // Every translation unit that includes this header must be compiled with -ffp-contract=off (Makefile): one rounding per
@@ -41,6 +43,10 @@ __device__ __forceinline__ bool inside_meshing(const Projected& q, float fW, flo
 }
 __device__ __forceinline__ bool inside_eval(const Projected& q, float fW, float fH) {
   return 0.f <= -q.z && q.u < fW && q.u > 0.f && q.v < fH && q.v > 0.f;
+}
+// meshing, point_masks' forecast frustum (reference slams/meshing.py:190-193, 224-227): the image widened by 1000 px on every side
+__device__ __forceinline__ bool inside_forecast(const Projected& q, float fW, float fH) {
+  return q.u < fW + 1000.f && q.u > -1000.f && q.v < fH + 1000.f && q.v > -1000.f && q.z < 0.f;
 }
 // meshing: the pixel a point reads, along one axis of `size` pixels
 __device__ __forceinline__ int round_pixel(float u, int size) { return min(max((int)rintf(u), 0), size - 1); }

@@ -1,4 +1,5 @@
-// Wave sum, workgroup scan and workspace alignment of the mesh and evaluation kernels (mesh, mesh_cc, mesh_eval, mesh_raster).
+// Wave sum and maximum, workgroup scan and workspace alignment of the mesh and evaluation kernels (mesh, mesh_cc, mesh_eval,
+// mesh_raster, mesh_masks).
 #pragma once
 #include "common.hpp"
 namespace dns {
@@ -8,6 +9,16 @@ template <class T>
 __device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+// The maximum over the 64 lanes, in every lane (order-independent).
+template <class T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T y = __shfl_xor(x, o);
+    x = y > x ? y : x;
+  }
   return x;
 }
 // Inclusive Hillis-Steele scan of one value per thread over a workgroup of exactly N threads, through s [N] in LDS: returns

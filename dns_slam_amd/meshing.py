@@ -8,6 +8,11 @@ A mapper trained with stem features (``mapper.encoder`` set) is meshed with ``st
 logit networks get_2d_feature's keyframe codes (meshing.py:311-377; csrc/mesh_feature.hip, ``ops.keyframe_codes``).  The
 geometry needs no codes -- the occupancy is the coarse / fine network's, which reads only the point encoding -- so the grid
 pass, marching cubes, cleaning and the component filter are the same with and without ``stem``.
+
+``Mesher.point_masks`` is the reference's split of points into seen / forecast / unseen (meshing.py:124-291; csrc/mesh_masks.hip,
+``ops.point_masks``) with its depth test and its all-frames branch; ``forecast=True`` is the reference's ``show_forecast`` mesh
+(fine decoders on the seen part of the grid, the coarse network on the forecast band, -100 elsewhere) and ``depth_test=True`` its
+``meshing.depth_test`` cleaning.
 """
 from __future__ import annotations
 
@@ -40,7 +45,8 @@ class Mesher:
         thr = m.get("remove_small_geometry_threshold")
         self.remove_small_geometry_threshold = None if thr is None else float(thr)
         if m.get("depth_test", False):
-            raise NotImplementedError("Mesher: depth_test=True (point_masks' rendered-depth test) is not supported")
+            raise NotImplementedError("Mesher: depth_test in the config is not read; pass depth_test=True to get_mesh / extract / "
+                                      "point_masks")
         if m.get("get_largest_components", False):
             raise NotImplementedError("Mesher: get_largest_components in the config is not read; pass components=\"largest\" to "
                                       "get_mesh / extract")
@@ -57,12 +63,12 @@ class Mesher:
         b, pad = self.marching_cubes_bound, 0.05
         return {"xyz": [np.linspace(b[a][0] - pad, b[a][1] + pad, n) for a in range(3)]}
 
-    def grid_points(self, xyz, s0, s1):
+    def grid_points(self, xyz, s0, s1=None):
         """Points s0..s1 of the reference's flattened meshgrid (indexing 'xy': point (j nx + i) nz + k = (x_i, y_j, z_k)),
-        fp32 as ``torch.tensor(..., dtype=torch.float)`` rounds them."""
+        fp32 as ``torch.tensor(..., dtype=torch.float)`` rounds them.  Without ``s1``, ``s0`` is an int64 tensor of point numbers."""
         x, y, z = (torch.tensor(a, dtype=torch.float64, device=self.device).float() for a in xyz)
         nx, nz = x.numel(), z.numel()
-        n = torch.arange(s0, s1, device=self.device)
+        n = torch.arange(s0, s1, device=self.device) if s1 is not None else s0
         return torch.stack((x[(n // nz) % nx], y[n // (nx * nz)], z[n % nz]), 1)
 
     def _keyframes(self, keyframe_dict, stem=None):
@@ -98,6 +104,48 @@ class Mesher:
             raise NotImplementedError("Mesher: a mapper with stem features (mapper.encoder set) needs get_2d_feature's 2-D codes "
                                       "through Merge; pass stem=True (or stem= the maps of Mesher.keyframe_stem) to compute them")
 
+    def _mask_args(self, keyframe_dict, all_frames=None, depth_test=False, depths=None):
+        """The mode of ``ops.point_masks`` for one extraction, as its keyword arguments (w2c included): the all-frames branch
+        (``all_frames = (estimate_c2w_list, idx)``: poses 0 .. idx, inverted in float64 as meshing.py:166-168 do), the depth test
+        against ``depths`` or the keyframes' gt_depth in chunks of points_batch_size, or the depth limit."""
+        dev = self.device
+        if all_frames is not None:
+            est, idx = all_frames
+            if est is None or idx is None:
+                raise ValueError("Mesher: all_frames is (estimate_c2w_list, idx)")
+            c2w = torch.as_tensor(est)[:int(idx) + 1].to(dev).double()
+            return {"w2c": torch.inverse(c2w).float()}
+        c2w = torch.stack([torch.as_tensor(kf["est_c2w"]).to(dev) for kf in keyframe_dict])
+        w2c = torch.inverse(c2w).float()                                     # meshing.py:206
+        dep = depths if depths is not None else torch.stack([torch.as_tensor(kf["gt_depth"]) for kf in keyframe_dict])
+        dep = torch.as_tensor(dep).to(dev).float()
+        if depth_test:
+            return {"w2c": w2c, "depths": dep, "chunk": self.points_batch_size}
+        return {"w2c": w2c, "max_depth": dep.reshape(dep.shape[0], -1).max(1).values}
+
+    def _classes(self, points, mask_args):
+        """``ops.point_masks`` of ``points`` in the mode of ``_mask_args``: [P] uint8, 0 unseen, 1 seen, 2 forecast."""
+        return ops.point_masks(points, mask_args["w2c"], self.cam, self.mapper.H, self.mapper.W,
+                               **{k: v for k, v in mask_args.items() if k != "w2c"})
+
+    @torch.no_grad()
+    def point_masks(self, points, keyframe_dict, estimate_c2w_list=None, idx=None, get_mask_use_all_frames=False, depth_test=False,
+                    depths=None):
+        """The reference's ``point_masks`` (meshing.py:124-291) -> (seen, forecast, unseen), bool [P] on the device; a point is
+        forecast only when no keyframe sees it.  ``get_mask_use_all_frames``: the frustum tests alone over the poses
+        ``estimate_c2w_list[:idx + 1]`` (each inverted in float64, then fp32), no depth rule.  Otherwise the keyframes'
+        ``torch.inverse(est_c2w)``, with the depth limit 1.2 max(gt_depth) or, with ``depth_test``, the occlusion test against the
+        keyframes' depth images in chunks of ``points_batch_size`` -- the forecast limit is each chunk's maximum depth sample, as
+        in the reference, so the forecast mask depends on points_batch_size.  ``depths`` [K,H,W] replaces the keyframes' gt_depth
+        in the depth test (and in the depth limit): it is the caller's hook for the reference's ``use_est_depth``, whose
+        ``depth_render`` cannot run in the reference itself and is not rebuilt here."""
+        if get_mask_use_all_frames and (estimate_c2w_list is None or idx is None):
+            raise ValueError("Mesher.point_masks: get_mask_use_all_frames needs estimate_c2w_list and idx")
+        points = torch.as_tensor(points).to(self.device).float()
+        cls = self._classes(points, self._mask_args(keyframe_dict, (estimate_c2w_list, idx) if get_mask_use_all_frames else None,
+                                                    depth_test, depths))
+        return cls == ops.MASK_SEEN, cls == ops.MASK_FORECAST, cls == ops.MASK_UNSEEN
+
     @torch.no_grad()
     def keyframe_stem(self, keyframe_dict, encoder=None, batch=4):
         """The stem maps of the keyframes' ``gt_color`` (``encoder`` or ``mapper.encoder``, ``batch`` keyframes per call) as
@@ -116,12 +164,18 @@ class Mesher:
         return out if out is not None else torch.zeros(0, 1, 1, 64, device=self.device)
 
     @torch.no_grad()
-    def grid_occupancy(self, keyframe_dict, stage="fine", kf=None, stem=None):
+    def grid_occupancy(self, keyframe_dict, stage="fine", kf=None, stem=None, forecast=False, depth_test=False, all_frames=None):
         """[nx, ny, nz] occupancy volume of the query grid (meshing.py:643-654: keyframe labels -> eval_points per
         points_batch_size chunk -> values[:, 3]) and the grid's axes.  ``stem`` only lifts the refusal of a mapper with an
         encoder and is not used: the reference computes get_2d_feature's codes for every grid chunk, but they reach only the
         colour and logit networks, and this pass keeps the occupancy alone, which the coarse / fine network forms from the
-        point encoding."""
+        point encoding.
+
+        ``forecast`` (the reference's show_forecast, meshing.py:601-641): the grid's point masks (``depth_test`` / ``all_frames``
+        as in ``point_masks``, taken per points_batch_size chunk of the grid); the seen points, compacted, get their keyframe
+        labels and the fine decoders of ``stage`` -- the > 1 point rule per points_batch_size chunk of the COMPACTED points, as
+        the reference's loop over ``points[seen_mask]`` has it --, the compacted forecast points the coarse network, the unseen
+        points -100."""
         self._check_supported(stem)
         kf = kf or self._keyframes(keyframe_dict)
         grid = self.get_grid_uniform()
@@ -129,6 +183,20 @@ class Mesher:
         P = nx * ny * nz
         B = self.points_batch_size
         step = B * max(1, (1 << 22) // B)                     # device chunks on points_batch_size boundaries
+        if forecast:
+            margs = self._mask_args(keyframe_dict, all_frames, depth_test)
+            cls = torch.cat([self._classes(self.grid_points(grid["xyz"], s0, min(s0 + step, P)), margs) for s0 in range(0, P, step)])
+            occ = torch.full((P,), -100.0, device=self.device)
+            for which, stg in ((ops.MASK_SEEN, stage), (ops.MASK_FORECAST, "coarse")):
+                idx = torch.nonzero(cls == which).reshape(-1)
+                for s0 in range(0, idx.numel(), step):
+                    n = idx[s0:s0 + step]
+                    pts = self.grid_points(grid["xyz"], n)
+                    label = None
+                    if stg != "coarse":
+                        label, _ = ops.keyframe_project(pts, kf[0], kf[1], kf[2], self.cam)
+                    occ[n] = self.mapper.eval_occupancy(pts, label, stage=stg, rule_chunk=B)
+            return occ.reshape(ny, nx, nz).permute(1, 0, 2).contiguous(), grid
         occ = torch.empty(P, device=self.device)
         for s0 in range(0, P, step):
             s1 = min(s0 + step, P)
@@ -140,13 +208,26 @@ class Mesher:
         return occ.reshape(ny, nx, nz).permute(1, 0, 2).contiguous(), grid
 
     @torch.no_grad()
-    def extract(self, keyframe_dict, stage="fine", clean_mesh=True, components=None, min_area=None, stem=None):
+    def extract(self, keyframe_dict, stage="fine", clean_mesh=True, components=None, min_area=None, stem=None, *, forecast=False,
+                depth_test=False, all_frames=None, bound_planes=None):
         """-> (verts [V,3] fp32 world / scale, faces [F,3] int32, colors [V,3] uint8, labels [V] int64), all on the device.
         ``components``: None, "small" (keep the components whose area exceeds ``min_area``, default
         ``cfg['meshing']['remove_small_geometry_threshold'] * scale * scale``) or "largest" (meshing.py:721-733); the filter
         runs on the cleaned mesh, ahead of the vertex query, and only with ``clean_mesh``.  ``stem``: None (a mapper without
-        stem features), True (run ``keyframe_stem``) or the [K,h,w,C] maps: the vertex query then uses the keyframe codes."""
+        stem features), True (run ``keyframe_stem``) or the [K,h,w,C] maps: the vertex query then uses the keyframe codes.
+
+        ``depth_test``: the cleaning keeps the faces with a vertex that passes ``point_masks``' depth test (the reference's
+        ``meshing.depth_test``).  ``all_frames = (estimate_c2w_list, idx)``: the masks -- of the cleaning and of ``forecast`` --
+        are those of get_mask_use_all_frames.  ``forecast`` (the reference's show_forecast): the volume of
+        ``grid_occupancy(forecast=True)``; the cleaning (meshing.py:695-708) drops the faces whose three vertices all lie outside
+        a convex bound, ``bound_planes`` [M,4]: a point x is inside when n . x + d <= 0 for every row (n, d) -- exactly
+        ``scipy.spatial.ConvexHull(...).equations``, in the scaled units of the marching-cubes bound; the reference's own bound,
+        get_bound_from_frames (a TSDF fusion of the keyframes and its hull), is not rebuilt, so ``forecast`` with ``clean_mesh``
+        and no ``bound_planes`` is refused.  The vertices whose mask is forecast are coloured (0, 255, 255) (:756-762)."""
         self._check_supported(stem)
+        if forecast and clean_mesh and bound_planes is None:
+            raise NotImplementedError("Mesher.extract: forecast=True with clean_mesh=True needs bound_planes= (the half-spaces of a "
+                                      "convex bound); the reference's get_bound_from_frames is not implemented")
         if components not in (None, "small", "largest"):
             raise ValueError(f"Mesher.extract: components must be None, 'small' or 'largest', got {components!r}")
         if components is not None and not clean_mesh:
@@ -157,21 +238,35 @@ class Mesher:
                                  "(or min_area=)")
             min_area = self.remove_small_geometry_threshold * self.scale * self.scale
         kf = self._keyframes(keyframe_dict, stem)
-        vol, grid = self.grid_occupancy(keyframe_dict, stage, kf, stem)
+        vol, grid = self.grid_occupancy(keyframe_dict, stage, kf, stem, forecast, depth_test, all_frames)
         x, y, z = grid["xyz"]
         verts, faces = ops.marching_cubes(vol, self.level_set, (x[0], y[0], z[0]), (x[2] - x[1], y[2] - y[1], z[2] - z[1]))
         if clean_mesh and faces.shape[0]:
-            verts, faces = self.clean(verts, faces, kf)
+            if forecast:
+                verts, faces = compact_mesh(verts, faces, inside_planes(verts, bound_planes)[faces.long()].any(1))[:2]
+            else:
+                verts, faces = self.clean(verts, faces, kf, depth_test,
+                                          self._mask_args(keyframe_dict, all_frames, depth_test) if depth_test or all_frames else None)
         if components == "small":
             verts, faces = self.filter_components(verts, faces, min_area=min_area)
         elif components == "largest":
             verts, faces = self.filter_components(verts, faces, largest=True)
         colors, labels = self.vertex_query(verts, kf, stage, stem)
+        if forecast and verts.shape[0]:
+            fore = self._classes(verts, self._mask_args(keyframe_dict, all_frames, depth_test)) == ops.MASK_FORECAST
+            colors[fore] = torch.tensor([0, 255, 255], dtype=torch.uint8, device=colors.device)
         return verts / self.scale, faces, colors, labels
 
-    def clean(self, verts, faces, kf):
-        """meshing.py:714-719: drop the faces whose three vertices no keyframe sees, then the vertices no face uses."""
-        _, seen = ops.keyframe_project(verts, kf[0], kf[1], kf[2], self.cam)
+    def clean(self, verts, faces, kf, depth_test=False, mask_args=None):
+        """meshing.py:714-719: drop the faces whose three vertices no keyframe sees, then the vertices no face uses.  With
+        ``mask_args`` (``_mask_args``: the depth test -- ``depth_test`` must then be set with it -- or the all-frames branch) seen
+        is ``point_masks``' in that mode."""
+        if depth_test and (mask_args is None or "depths" not in mask_args):
+            raise ValueError("Mesher.clean: depth_test needs mask_args=_mask_args(keyframe_dict, depth_test=True)")
+        if mask_args is not None:
+            seen = self._classes(verts, mask_args) == ops.MASK_SEEN
+        else:
+            _, seen = ops.keyframe_project(verts, kf[0], kf[1], kf[2], self.cam)
         return compact_mesh(verts, faces, seen[faces.long()].any(1))[:2]
 
     def filter_components(self, verts, faces, min_area=None, largest=False):
@@ -213,14 +308,17 @@ class Mesher:
 
     def get_mesh(self, mesh_out_file, keyframe_dict, idx, color=True, label=False, palette=None, show_forecast=False,
                  element=False, clean_mesh=None, stage="fine", remove_small_geometry=False, fill_holes=False, components=None,
-                 min_area=None, stem=None):
+                 min_area=None, stem=None, *, forecast=False, depth_test=False, all_frames=None, bound_planes=None):
         """Writes ``{mesh_out_file}/mesh_{idx}.ply`` (vertex colours when ``color``, the vertex labels as an int property) and,
         with ``label`` and a ``palette`` (class -> RGB: an [n_class, 3] array, a dict or a callable like the reference's
         v_map_function), ``mesh_{idx}_semantic.ply``.  Returns the paths written.  ``components`` / ``min_area``: the
-        connected-components filter of ``extract`` (meshing.py:721-733); ``stem``: as in ``extract``.  fill_holes (meshing.py:770) is not implemented and,
-        like the reference's own spellings of the filters and of the per-class meshes, refused when asked for."""
+        connected-components filter of ``extract`` (meshing.py:721-733); ``stem``, ``forecast`` (the reference's show_forecast),
+        ``depth_test``, ``all_frames`` and ``bound_planes``: as in ``extract``.  fill_holes (meshing.py:770) is not implemented and,
+        like the reference's own spellings of the filters, of the forecast mesh and of the per-class meshes, refused when asked
+        for."""
         if show_forecast:
-            raise NotImplementedError("Mesher.get_mesh: show_forecast is not supported")
+            raise NotImplementedError("Mesher.get_mesh: show_forecast is not a keyword here; pass forecast=True (with bound_planes= "
+                                      "when the mesh is cleaned)")
         if element:
             raise NotImplementedError("Mesher.get_mesh: element is not a keyword here; the per-class meshes are written by "
                                       "Mesher.get_part_meshes")
@@ -230,7 +328,8 @@ class Mesher:
         if fill_holes:
             raise NotImplementedError("Mesher.get_mesh: fill_holes is not supported")
         verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh,
-                                                    components, min_area, stem)
+                                                    components, min_area, stem, forecast=forecast, depth_test=depth_test,
+                                                    all_frames=all_frames, bound_planes=bound_planes)
         v, f, lab = verts.cpu().numpy(), faces.cpu().numpy(), labels.cpu().numpy()
         os.makedirs(mesh_out_file, exist_ok=True)
         out = [os.path.join(mesh_out_file, f"mesh_{idx}.ply")]
@@ -241,13 +340,13 @@ class Mesher:
         return out
 
     def get_part_meshes(self, mesh_out_file, keyframe_dict, idx, color=True, stage="fine", clean_mesh=None, components=None,
-                        min_area=None, stem=None):
+                        min_area=None, stem=None, depth_test=False):
         """The reference's ``element`` branch (meshing.py:786-825): for every distinct vertex label e of the extracted mesh,
         the faces with at least one vertex labelled e, compacted, as ``{mesh_out_file}/mesh_{idx}_part_{int(e)}.ply``.  Colours
-        and labels are those of the full mesh's vertex query, not queried again per part.  ``stem``: as in ``extract``.  Returns
-        the paths written."""
+        and labels are those of the full mesh's vertex query, not queried again per part.  ``stem``, ``depth_test``: as in
+        ``extract``.  Returns the paths written."""
         verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh,
-                                                    components, min_area, stem)
+                                                    components, min_area, stem, depth_test=depth_test)
         os.makedirs(mesh_out_file, exist_ok=True)
         out = []
         for e in torch.unique(labels).tolist():
@@ -256,6 +355,15 @@ class Mesher:
             write_ply(out[-1], v.cpu().numpy(), f.cpu().numpy(), colors[used].cpu().numpy() if color else None,
                       labels[used].cpu().numpy())
         return out
+
+
+def inside_planes(points, planes):
+    """bool [P]: the points [P,3] inside the convex region of the half-spaces ``planes`` [M,4], n . x + d <= 0 for every row
+    (n, d) (``scipy.spatial.ConvexHull.equations``); float64, ((n0 x + n1 y) + n2 z) + d in that order."""
+    pl = torch.as_tensor(planes).to(points.device).double().reshape(-1, 4)
+    p = points.double()
+    val = ((p[:, None, 0] * pl[None, :, 0] + p[:, None, 1] * pl[None, :, 1]) + p[:, None, 2] * pl[None, :, 2]) + pl[None, :, 3]
+    return (val <= 0).all(1)
 
 
 def compact_mesh(verts, faces, keep):

@@ -968,6 +968,63 @@ def keyframe_project(points: torch.Tensor, w2c: torch.Tensor, labels: torch.Tens
     return label, seen.bool()
 
 
+# ----------------------------------------------------------------------------- point masks (csrc/mesh_masks.hip)
+MASK_UNSEEN, MASK_SEEN, MASK_FORECAST = 0, 1, 2
+
+
+@torch.no_grad()
+def point_masks(points: torch.Tensor, w2c: torch.Tensor, cam: dict, H: int, W: int, *, max_depth: Optional[torch.Tensor] = None,
+                depths: Optional[torch.Tensor] = None, chunk: Optional[int] = None):
+    """point_masks of the reference (meshing.py:124-291): points [P,3] world, w2c [K,4,4] fp32 world->camera, cam
+    {'fx','fy','cx','cy'}, image size H x W -> cls [P] uint8, 0 = unseen, 1 = seen, 2 = forecast (a point is forecast only when no
+    pose sees it).  Three modes (include/dns_hip.h):
+      neither ``max_depth`` nor ``depths``   the frustum tests alone (get_mask_use_all_frames, :164-201);
+      ``max_depth`` [K]                      both masks need -cam_z < 1.2 max_depth[k] (:257-271); seen is keyframe_project's;
+      ``depths`` [K,H,W] and ``chunk``       the depth test (:229-255) against the bilinear sample of the keyframe's depth; the
+                                             forecast limit is the maximum sample over the point's ``chunk``-point chunk, as the
+                                             reference's per-points_batch_size torch.max -- the result depends on ``chunk``.
+    P = 0 or K = 0: all unseen, nothing is launched."""
+    who = "point_masks"
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{who}: points [P,3]")
+    if points.shape[0] >= 1 << 31:
+        raise ValueError(f"{who}: {points.shape[0]} points (must be < 2^31)")
+    if max_depth is not None and depths is not None:
+        raise ValueError(f"{who}: max_depth (depth limit) and depths (depth test) exclude each other")
+    if depths is not None and chunk is None:
+        raise ValueError(f"{who}: the depth test needs chunk (the reference's points_batch_size)")
+    if depths is None and chunk is not None:
+        raise ValueError(f"{who}: chunk is the depth test's; pass depths with it")
+    if chunk is not None and not 0 < int(chunk) < 1 << 32:
+        raise ValueError(f"{who}: chunk must be in 1 .. 2^32 - 1, got {chunk}")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: image of {H} x {W}")
+    pts, w, K = _pose_args(who, points, w2c)
+    md = dep = None
+    if max_depth is not None:
+        md = max_depth.detach().contiguous().float().reshape(-1)
+        require_cuda(md)
+        if md.numel() != K:
+            raise ValueError(f"{who}: w2c [K,4,4] and max_depth [K] with one K, got {tuple(w.shape)} and {tuple(max_depth.shape)}")
+    if depths is not None:
+        dep = depths.detach().contiguous().float()
+        require_cuda(dep)
+        if tuple(dep.shape) != (K, H, W):
+            raise ValueError(f"{who}: depths must be [K,H,W] = {(K, H, W)}, got {tuple(dep.shape)}")
+    P, dev = int(pts.shape[0]), pts.device
+    if P == 0 or K == 0:
+        return torch.zeros(P, dtype=torch.uint8, device=dev)
+    cls = torch.empty(P, dtype=torch.uint8, device=dev)
+    ws, c = None, 0
+    if dep is not None:
+        c = min(int(chunk), P)                               # a chunk beyond P is the one chunk of P points
+        ws = torch.empty(int(_rawlib.dns_point_masks_ws_bytes(P, K, c)), dtype=torch.uint8, device=dev)
+    check(lib.dns_point_masks(ptr(pts), P, ptr(w), K, ptr(md), ptr(dep), c, H, W, _intrinsics(cam["fx"], cam["fy"], cam["cx"], cam["cy"]),
+                              ptr(ws), ptr(cls), stream_ptr()), "dns_point_masks")
+    return cls
+
+
 # ----------------------------------------------------------------------------- keyframe codes (csrc/mesh_feature.hip)
 KF_WORKSPACE_BYTES = 1 << 30                 # default budget of keyframe_codes' row, latent, record and relative-point buffers
 

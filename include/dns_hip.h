@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 19
+#define DNS_ABI_VERSION 20
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -824,6 +824,29 @@ int dns_kf_pair_rows(const int32_t* records, uint64_t n, const float* pts, uint3
                      void* stream);
 int dns_kf_code_mean(const float* latents, uint32_t ld_lat, uint64_t n, const int64_t* offset, const int32_t* count, uint32_t P,
                      uint32_t D, float* code, void* stream);
+
+/* ---- point masks (Mesher.point_masks, slams/meshing.py:124-291; csrc/mesh_masks.hip; ABI v20) --------------------------------
+ * cls [P] uint8 = 0 unseen, 1 seen, 2 forecast for the points pts [P,3] fp32 against the K poses w2c [K,16] fp32 (row-major
+ * world->camera), under dns_keyframe_project's projection (intr [host] = fx, fy, cx, cy).  Pose k has the point INSIDE when
+ * 0 < u < W, 0 < v < H and z < 0, and in its FORECAST FRUSTUM when -1000 < u < W + 1000, -1000 < v < H + 1000 and z < 0.  A point
+ * is seen when some pose has it inside and that pose's depth rule for seeing holds; forecast when it is not seen and some pose has
+ * it in the forecast frustum under that pose's rule for forecasting.  With dz = -cam_z the rules are, by mode:
+ *   frustum only (max_depth NULL, depths NULL; get_mask_use_all_frames, :164-201): none.
+ *   depth limit  (max_depth [K] = the maximum of each keyframe's gt_depth; :257-271): dz < 1.2 max_depth[k] for both; the seen
+ *     points are dns_keyframe_project's, the same bits.
+ *   depth test   (depths [K,H,W] fp32, chunk > 0 = the reference's points_batch_size; :229-255): ds = the bilinear sample of
+ *     depths[k] at (u, v) with pixel i at coordinate i and taps outside the image contributing 0 (F.grid_sample, zeros padding,
+ *     align_corners=True); seeing needs dz < ds + 0.1 and ds - 2.5 < dz; forecasting needs dz < m[c,k], the maximum of ds over ALL
+ *     points of the point's chunk c = p / chunk, whatever frustum they lie in (torch.max(depth_sample), :243: the result depends
+ *     on the chunk length, as the reference's does; chunk >= P is one chunk).  Two passes: the table m [n_chunks, K] is built in
+ *     ws by integer atomic maxima (order-independent: the same bits for every call), then the classes.  The library presets the
+ *     table; dns_point_masks_ws_bytes gives its size (0 when none is needed or the size is refused).
+ * A non-finite (u, v) (cam_z + 1e-8 == 0) samples as 0 and is inside nothing; the reference carries a NaN into the chunk maximum
+ * there.  P = 0: nothing is launched.  K = 0: every point is unseen.  Refused: P >= 2^31, both max_depth and depths, depths with
+ * chunk == 0, chunk != 0 without depths, H or W < 1, a depth test without ws. */
+uint64_t dns_point_masks_ws_bytes(uint32_t P, uint32_t K, uint32_t chunk);
+int dns_point_masks(const float* pts, uint32_t P, const float* w2c, uint32_t K, const float* max_depth, const float* depths,
+                    uint32_t chunk, int H, int W, const float* intr, void* ws, uint8_t* cls, void* stream);
 
 #ifdef __cplusplus
 }
