@@ -33,7 +33,8 @@ import os
 import torch
 
 from . import ops
-from ._lib import DnsAdamTensor, DnsSplitRows, DnsTrackFused, check, ptr
+from ._lib import DnsAdamTensor, DnsTrackFused, check, ptr
+from .launch import Fp32Rows, HalfRows, Net, SplitRows, Stem2D, aligned_floats, alloc_ray_buffers
 from .common import get_quad_from_c2w, get_rotation_from_quad
 
 _V = C.c_void_p
@@ -48,6 +49,26 @@ def _morton2(row, col):
         v = (v | (v << 2)) & 0x33333333
         return (v | (v << 1)) & 0x55555555
     return spread(col) | (spread(row) << 1)
+
+
+def _read_scene(o, who, dec, features, refer_frames, maps, refer):
+    """What both steps read of the decoder and of ``features`` -- None | the per-sample code [N, S, C] | the stem feature maps
+    (``maps`` names their shape; + refer_frames, ``refer`` names what they hold): with stem maps the 2-D branch, feature_matching +
+    Decoder.merge, runs INSIDE every iteration (launch.Stem2D)."""
+    o.stem = features is not None and features.dim() == 5
+    if features is not None and features.dim() not in (3, 5):
+        raise ValueError(f"{who}: features is the per-sample code [N, S, C] or the stem feature maps {maps}")
+    if o.stem and refer_frames is None:
+        raise ValueError(f"{who}: stem feature maps need {refer}")
+    o.features = None if (features is None or o.stem) else features.to(o.dev).float().contiguous()
+    nets = (dec.coarse_fn.decoder, dec.out_fn.color_decoder, dec.out_fn.logit_decoder) + ((dec.merge.decoder,) if o.stem else ())
+    o.fp16 = ops.MLP_FP16_FLAG if getattr(nets[0], "fp16", False) else 0
+    shapes = [(n.n_input_dims, n.n_output_dims, n.n_neurons, n.n_hidden_layers) for n in nets]
+    (o.shp_c, o.shp_col, o.shp_log), (o.p_coarse, o.p_color, o.p_logit) = shapes[:3], (n.params for n in nets[:3])
+    if o.stem:
+        o.shp_m, o.p_merge = shapes[3], nets[3].params
+    o.p_table, o.meta, o.n_bins = dec.pe_fn.grid_fn.params, dec.pe_fn.grid_fn.meta, dec.pe_fn.pe_fn.n_bins
+    return nets[:3]
 
 
 class _Set:
@@ -65,14 +86,9 @@ class MapStep:
             raise ValueError("dns_slam_amd ops run on the GPU only; there is no CPU fallback")
         if not (m.static_shapes and m.fused_losses):
             raise ValueError("MapStep needs mapper.static_shapes and mapper.fused_losses (the sync-free iteration)")
-        # features: None | the per-sample code [N, S, C] | the stem feature maps [n_target, n_refer, C, h, w] of the reference
-        # views (+ refer_frames): then the 2-D branch of slams/mapping.py:532-557 -- feature_matching + Decoder.merge -- runs
-        # INSIDE every step, forward and backward (Merge's weights train, its OneBlob input carries pose gradient)
-        self.stem = features is not None and features.dim() == 5
-        if features is not None and features.dim() not in (3, 5):
-            raise ValueError("MapStep: features is the per-sample code [N, S, C] or the stem feature maps [K, R, C, h, w]")
-        if self.stem and refer_frames is None:
-            raise ValueError("MapStep: stem feature maps need refer_frames (kf_idx, est_c2w)")
+        # (stem feature maps: slams/mapping.py:532-557, forward and backward -- Merge's weights train, its OneBlob input carries
+        #  pose gradient)
+        nets = _read_scene(self, "MapStep", m.decoder, features, refer_frames, "[K, R, C, h, w]", "refer_frames (kf_idx, est_c2w)")
         self.dist_on = m.dist is not None and m.dist.enabled       # (a forced one-rank group counts: tests drive RCCL that way)
         self.world = m.dist.world_size if self.dist_on else 1
         # union-batch mode (dist.py, SURVEY 8e's partitioning): every rank draws the SAME lists; this rank renders rays [a, b) of
@@ -82,7 +98,6 @@ class MapStep:
         self.prep = prep if prep is not None else m.prepare_frames(target_frames)
         self.npf_g = self.prep["n1"] + self.prep["n2"]                     # rays per frame of the whole (drawn) list
         self.ray_a, self.ray_b = m.dist.shard(self.npf_g) if self.union else (0, self.npf_g)
-        self.features = None if (features is None or self.stem) else features.to(dev).float().contiguous()
         if self.features is not None and self.union:                        # the code of the rank's rays
             K_ = m.n_target_frame
             fs = self.features
@@ -93,12 +108,8 @@ class MapStep:
         K = self.K = m.n_target_frame
         dec, pool = m.decoder, m.fine_decoders
         self.pe_dim, self.grid_dim, self.hid = m.pe_dim, m.grid_dim, m.hidden_dim
-        nets = (dec.coarse_fn.decoder, dec.out_fn.color_decoder, dec.out_fn.logit_decoder)
         if any(getattr(n, "fp16", False) != getattr(nets[0], "fp16", False) for n in nets):
             raise ValueError("MapStep: the networks must share one operand precision")
-        self.fp16 = ops.MLP_FP16_FLAG if getattr(nets[0], "fp16", False) else 0
-        shp = lambda n: (n.n_input_dims, n.n_output_dims, n.n_neurons, n.n_hidden_layers)
-        self.shp_c, self.shp_col, self.shp_log = (shp(n) for n in nets)
         self.shp_f = (self.pe_dim + self.grid_dim, self.hid + 1, pool.nn_, pool.nl)
         # width of the colour / logit networks' second input segment: (fine latents | 2-D code).  WITHOUT a code (features None:
         # the reference multiplies a zero code through, slams/mapping.py:553-557) the code columns are identically zero: the
@@ -126,23 +137,14 @@ class MapStep:
         self.pose_row0 = 0 if K == 1 else 1
 
         # ---- parameters and the flat gradient buffer  [colour | logit | pool | table | coarse | quat | trans]
-        self.p_table = dec.pe_fn.grid_fn.params
-        self.meta = dec.pe_fn.grid_fn.meta
-        self.n_bins = dec.pe_fn.pe_fn.n_bins
-        self.p_coarse, self.p_color, self.p_logit = (n.params for n in nets)
         self.p_pool = pool.pool
         # [colour | logit | pool | merge (with stem features) || table | coarse | quat | trans]: what stands in front of the bar is
         # complete when the ray branch's MLP backward ends (the early all-reduce bucket under data parallelism)
-        names = ["color", "logit", "pool"] + (["merge"] if self.stem else []) + ["table", "coarse", "quat", "trans"]
-        if self.stem:
-            mg = dec.merge.decoder
-            self.shp_m = shp(mg)
-            self.p_merge = mg.params
-        byname = {"color": self.p_color, "logit": self.p_logit, "pool": self.p_pool, "table": self.p_table, "coarse": self.p_coarse,
-                  "quat": self.Q, "trans": self.T}
+        byname = {"color": self.p_color, "logit": self.p_logit, "pool": self.p_pool}
         if self.stem:
             byname["merge"] = self.p_merge
-        plist = [byname[n] for n in names]
+        byname.update(table=self.p_table, coarse=self.p_coarse, quat=self.Q, trans=self.T)
+        names, plist = list(byname), list(byname.values())
         for p in plist:
             if not (p.is_cuda and p.is_contiguous() and p.dtype == torch.float32):
                 raise ValueError("MapStep: parameters must be contiguous fp32 CUDA tensors")
@@ -170,7 +172,7 @@ class MapStep:
                 it.n, it.lr = n, lr
             return arr
 
-        # ---- ray-branch buffers
+        # ---- the row format of the MLP input, chosen ONCE (launch.py); the ray branch and the lattice each get their rows below
         npf = self.npf = self.ray_b - self.ray_a
         nu = 0 if m.t_uniform is None else m.t_uniform.numel()
         ns = m.n_surface_ray
@@ -178,20 +180,12 @@ class MapStep:
         P = N * S
         self.N, self.S, self.P, self.nu, self.ns = N, S, P, nu, ns
         f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        self.rays_o, self.rays_d, self.gt_color, self.gt_depth = f(N, 3), f(N, 3), f(N, 3), f(N)
-        self.gt_label = torch.empty(N, device=dev, dtype=torch.int64)
-        self.inside = torch.empty(N, device=dev, dtype=torch.uint8)
-        self.z, self.pts = f(N, S), f(N, S, 3)
         ld = self.ld = self.pe_dim + self.grid_dim
-        self.x3, self.buf = f(P, 3), f(P, ld)
-        self.dydx = f(self.meta.n_levels * 3 * P * 2) if self.is_BA else None
-        # Split rows (include/dns_hip.h, ABI v9): the encoder and the feature block write their rows ONCE in the form the MLP
-        # kernels' matrix instructions take (f16 hi | lo halfs + one exponent per row) and every forward / backward launch loads
-        # its operand fragments straight from memory; the fp32 rows are still written for the streaming dW_in kernels.
-        # Measured (round 4): the MLP kernels do NOT get faster at fp32 grade (vector instructions -12 %,
-        # time +-0: they are not bound by their input handling; cfg2 step 1.89 -> 2.04 ms) and with half-width networks the
-        # forward's gain (0.60 -> 0.49 ms at cfg5_fp16) is eaten by the encoder writing a second row format (0.40 -> 0.51):
-        # 6.19 -> 6.34 ms.  OFF by default; DNS_SPLIT_ROWS=1 / split_rows=True turns it on (tests/test_gpu_split_rows.py).
+        # Split rows (launch.SplitRows).  Measured (round 4): the MLP kernels do NOT get faster at fp32
+        # grade (vector instructions -12 %, time +-0: they are not bound by their input handling; cfg2 step 1.89 -> 2.04 ms) and
+        # with half-width networks the forward's gain (0.60 -> 0.49 ms at cfg5_fp16) is eaten by the encoder writing a second row
+        # format (0.40 -> 0.51): 6.19 -> 6.34 ms.  OFF by default; DNS_SPLIT_ROWS=1 / split_rows=True turns it on (the kernels:
+        # tests/test_gpu_split_rows.py; the step on them: tests/test_gpu_fused_step.py, tests/test_gpu_mlp_half.py).
         if split_rows is None:
             split_rows = os.environ.get("DNS_SPLIT_ROWS", "0") == "1"
         self.sr = bool(split_rows) and ld % 16 == 0 and self.pe_dim % 16 == 0 and self.n_feat % 16 == 0 and not keep_hidden
@@ -201,24 +195,26 @@ class MapStep:
         # once per step on the side stream under the ray branch's sampling / encoding) instead of building them per workgroup:
         # -10..17 us per backward launch and -2..6 us per forward launch since the copy-in keeps eight requests in flight.
         # mapper.prepared_images = False keeps the per-workgroup build; the split-row form takes fp32 weights
-        # ---- HALF ROWS (ABI v12): networks that ask for tcnn's own precision (cfg['model']['mlp']['dtype'] = 'fp16', BASELINE
-        # configs[4]) run on the native f16 kernels -- the encoder and the feature block write plain f16 rows, every network launch
-        # reads them, ONE backward kernel per network forms all gradients (no dH_1 workspace, no dns_mlp_dwin), gradients carry
-        # tcnn's static loss scale (mapper.loss_scale, default 128).  mapper.half_rows = False / DNS_HALF_ROWS=0 keeps round 4's
-        # fp16-OPERAND mode of the split-operand kernels (per-point scales on fp32 rows).  The in-step 2-D branch (stem features)
-        # and kept hidden activations are not wired to it.
+        # ---- HALF ROWS (launch.HalfRows) for networks that ask for tcnn's own precision (cfg['model']['mlp']['dtype'] = 'fp16',
+        # BASELINE configs[4]; loss scale: mapper.loss_scale, default 128).  mapper.half_rows = False / DNS_HALF_ROWS=0 keeps round
+        # 4's fp16-OPERAND mode of the split-operand kernels (per-point scales on fp32 rows).  The in-step 2-D branch (stem
+        # features) and kept hidden activations are not wired to it.
         self.half = (bool(self.fp16) and bool(getattr(m, "half_rows", os.environ.get("DNS_HALF_ROWS", "1") != "0")) and not self.stem
                      and not keep_hidden and not self.sr and ld % 16 == 0 and self.pe_dim % 8 == 0 and self.n_feat % 8 == 0
                      and (self.pe_dim + self.n_feat) % 16 == 0)
         self.loss_scale = float(getattr(m, "loss_scale", ops.HALF_LOSS_SCALE))
         if self.half:
-            self.xh = torch.empty(P, ld, device=dev, dtype=torch.float16)
-            self.feath = torch.empty(P, self.n_feat, device=dev, dtype=torch.float16)
+            new_rows = lambda n, n_feat: HalfRows(n, ld, self.pe_dim, n_feat, dev, self.live, self.loss_scale)
+        elif self.sr:
+            new_rows = lambda n, n_feat: SplitRows(n, ld, self.pe_dim, n_feat, dev, bool(self.fp16))
+        else:
+            null_split = (self.n_feat if self.fp16 else 2 * self.n_feat, 1 if self.fp16 else 0)
+            new_rows = lambda n, n_feat: Fp32Rows(n, ld, self.pe_dim, n_feat, dev, self.live, null_split)
         self.use_prep = (bool(getattr(m, "prepared_images", os.environ.get("DNS_PREPARED_IMAGES", "1") != "0")) and not self.sr
                          and not self.half)
-        self._blobs, self._prep_jobs = {}, []
+        raw_lib = ops.lib._raw
+        blobs, self._prep_jobs = {}, []
         if self.use_prep:
-            raw_lib = ops.lib._raw
             G = int(self.p_pool.shape[0]) if self.p_pool.dim() == 2 else 1
             live_n = (self.live >> 16) & 0xff
             jobs = [(self.p_coarse, self.shp_c, self.shp_c[1], 1, 0, 0),            # (params, shape, n_out, n_sets, stride, live flag)
@@ -229,28 +225,37 @@ class MapStep:
             for prm, shp_, n_out, n_sets, stride, lv in jobs:
                 n_in_eff = live_n if lv else shp_[0]
                 nfl = int(raw_lib.dns_mlp_prepared_floats(n_in_eff, n_out, shp_[2], shp_[3]))
-                blob = torch.empty(nfl * n_sets + 64, device=dev)
-                off = (-blob.data_ptr() // 4) % 4                      # 16-byte aligned start
-                view = blob[off:off + nfl * n_sets]
-                self._blobs[(prm.data_ptr(), n_out)] = view
-                self._prep_jobs.append((prm, shp_[0], n_out, shp_[2], shp_[3], n_sets, stride, view, lv, blob))
-        self.sr_planes = 1 if self.fp16 else 2           # half-width networks read the hi plane only
-        self.sr_flags = 1 if self.fp16 else 0            # DNS_SPLIT_HI_ONLY
-        if self.sr:
-            np_ = self.sr_planes
-            h16 = lambda *s_: torch.empty(*s_, device=dev, dtype=torch.float16)
-            i32 = lambda n_: torch.empty(n_, device=dev, dtype=torch.int32)
-            self.xs, self.xexp = h16(P, np_ * ld), i32(P)
-            self.fxs, self.fexp = h16(P, np_ * self.n_feat), i32(P)
-            self.rows_x = DnsSplitRows(self.xs.data_ptr(), self.xexp.data_ptr(), np_ * ld, ld if np_ == 2 else 0)
-            self.rows_f = DnsSplitRows(self.fxs.data_ptr(), self.fexp.data_ptr(), np_ * self.n_feat, self.n_feat if np_ == 2 else 0)
+                view = blobs[(prm.data_ptr(), n_out)] = aligned_floats(nfl * n_sets, 4, dev)
+                self._prep_jobs.append((prm, shp_[0], n_out, shp_[2], shp_[3], n_sets, stride, view, lv))
+
+        def net(params, shape, n_out=None, **kw):
+            """A network of the step as the row formats take it: its prepared images where the step builds them."""
+            shape = shape if n_out is None else (shape[0], n_out) + tuple(shape[2:])
+            blob = blobs.get((params.data_ptr(), shape[1]))
+            return Net(params, shape, self.fp16, **kw) if blob is None else Net(blob, shape, self.fp16 | ops.MLP_PREPARED_FLAG, **kw)
+
+        # ---- ray-branch buffers
+        alloc_ray_buffers(self, N, S, self.n_class, self.n_feat, dev)
+        rows = self.rows = new_rows(P, self.n_feat)
+        self.buf, self.feat = rows.buf, rows.feat      # (None on half rows)
+        self.dydx = f(self.meta.n_levels * 3 * P * 2) if self.is_BA else None
         nf = self.hid + 1
-        self.coarse = f(P, nf)
+        self.coarse, self.d_coarse = f(P, nf), f(P, nf)
+        self.d_fine = self.d_featx[:, 3:3 + nf]        # the fine network's output gradient: the losses write it THERE, compositing
+        self.d_buf = f(P, ld)                          # adds d occupancy, the colour / logit networks add (+=) theirs: no sum kernel
         n_groups = self.n_groups = max(len(pool), 1)
         self.n_slots = (P + 127) // 128 * 128 + 128 * n_groups
         self.group_ws = torch.empty(512, device=dev, dtype=torch.int32)
-        self.feat = f(P, self.n_feat)
         self.slot = torch.empty(P, device=dev, dtype=torch.int64)
+        # Hidden activations kept by the forward for the backward (dns_mlp_fwd h_save -> dns_mlp_bwd h_saved) instead of being
+        # recomputed: stand-alone the backward kernel is 17 % faster (122 -> 101 us) and the forward 18 % slower (46 -> 54 us),
+        # but in this two-stream step the extra 0.76 GB of traffic per iteration costs more than the vector work it saves
+        # (1.917 -> 1.944 ms with every network keeping them, 1.915 with the lattice branch alone): off by default
+        hbuf = lambda n_slots, s: f(s[3] * n_slots * s[2]) if keep_hidden else None
+        self.net_c = net(self.p_coarse, self.shp_c, hidden=hbuf(P, self.shp_c))
+        self.net_col = net(self.p_color, self.shp_col, hidden=hbuf(P, self.shp_col))
+        self.net_log = net(self.p_logit, self.shp_log, hidden=hbuf(P, self.shp_log))
+        h_f = hbuf(self.n_slots, self.shp_f)
         # two alternating sets of everything a step's preparation writes (see _prepare)
         self.sets = []
         for _ in range(2):
@@ -264,33 +269,21 @@ class MapStep:
             st_.adam_items = adam_items(st_.G)
             st_.row_index = torch.empty(self.n_slots, device=dev, dtype=torch.int32)
             st_.tile_group = torch.empty(self.n_slots // 128, device=dev, dtype=torch.int32)
+            st_.net_pool = net(self.p_pool, self.shp_f, stride=int(self.p_pool.shape[-1]), hidden=h_f,
+                               table=(st_.row_index, st_.tile_group, self.n_slots))
             st_.ev, st_.draws, st_.dmax = None, None, None
             self.sets.append(st_)
         self.cur = self.sets[0]
-        self.raw, self.logit = f(P, 4), f(P, self.n_class)
-        self.depth, self.var, self.rgb, self.weights, self.sem = f(N), f(N), f(N, 3), f(N, S), f(N, self.n_class)
-        self.sums_ws, self.out = f(ops.LOSS_SUMS_FLOATS), f(16)
-        self.one = torch.ones(1, device=dev)
-        self.d_color, self.d_depth, self.d_sem = f(N, 3), f(N), f(N, self.n_class)
-        self.d_coarse = f(P, nf)
-        self.d_raw, self.d_logit, self.d_col = f(P, 4), f(P, self.n_class), f(P, 4)
-        self.d_buf = f(P, ld)
-        self.d_featx = torch.zeros(P, 4 + self.n_feat, device=dev)        # zeroed once: the code columns only accumulate
-        self.d_x3 = f(P, 3)
-        raw_lib = ops.lib._raw
         if self.stem:
             Kf, R, Cs, fh, fw = features.shape
             if Kf != K:
                 raise ValueError("MapStep: stem feature maps must have one set of reference views per target frame")
-            self.R, self.Cs, self.fh, self.fw = int(R), int(Cs), int(fh), int(fw)
+            self.R = int(R)
             self.feat_maps = features.detach().to(dev).float().permute(0, 1, 3, 4, 2).contiguous().reshape(K * R, fh, fw, Cs)
-            mrg = dec.merge
-            self.n_bins_m = mrg.pe_fn.n_bins
-            self.pe_m = 3 * self.n_bins_m
-            n_in_m, n_out_m = self.shp_m[0], self.shp_m[1]
-            if not (n_in_m == self.pe_m + Cs and n_out_m == self.hid and self.pe_m % 4 == 0):
-                raise ValueError("MapStep: Decoder.merge's network does not match the stem features / hidden width")
-            self.b6m = ops._bound6(mrg.bound)
+            self.Pf = npf * S                                             # points per target frame
+            self.stem2d = Stem2D("MapStep", dec.merge, K, R, self.Pf, Cs, fh, fw, self.hid, (m.fx, m.fy, m.cx, m.cy), dev,
+                                 want_dw=True, want_pose=self.is_BA)
+            self.net_m = Net(self.p_merge, self.shp_m, self.fp16)
             # which pose every reference view takes (slams/mapping.py:534-545): -1 = the target frame itself, a keyframe that is
             # also a target = that target's pose under optimisation, anything else = the stored keyframe pose
             target_idx = list(target_frames["kf_idx"])
@@ -306,25 +299,12 @@ class MapStep:
             self.ref_src = torch.tensor(src, dtype=torch.int32, device=dev)
             self.ref_fixed = torch.stack(fixed).contiguous()
             self.w2c, self.origin = f(K * R, 16), f(K * R, 3)
-            Mr = self.Mr = R * P
-            self.Pf = npf * S                                             # points per target frame
-            self.mbuf, self.rel, self.xm = f(Mr, n_in_m), f(Mr, 3), f(Mr, 3)
-            self.mlat, self.mdy = f(Mr, n_out_m), f(Mr, n_out_m)
-            self.d_mpe, self.d_rel = (f(Mr, self.pe_m), f(Mr, 3)) if self.is_BA else (None, None)
-            self.ws_m = f(max(int(raw_lib.dns_mlp_bwd_ws_floats(Mr, self.shp_m[2], self.shp_m[3])), 4))
-            self.K9 = (C.c_float * 9)(float(m.fx), 0.0, float(m.cx), 0.0, float(m.fy), float(m.cy), 0.0, 0.0, 1.0)
         self.ray_ws = f(max(int(raw_lib.dns_raygen_bwd_ws_floats(K, npf)), 1))
         mlp_ws = lambda n_slots, s: f(max(int(raw_lib.dns_mlp_bwd_ws_floats(n_slots, s[2], s[3])), 4))
         self.ws_mlp = max((mlp_ws(self.n_slots, s) for s in (self.shp_f, self.shp_c, self.shp_col, self.shp_log)),
                           key=lambda t: t.numel())
         self.ws_mlp4 = [self.ws_mlp] + [torch.empty_like(self.ws_mlp) for _ in range(3)]   # one per network when dW_in is forked
-        # Hidden activations kept by the forward for the backward (dns_mlp_fwd h_save -> dns_mlp_bwd h_saved) instead of being
-        # recomputed: stand-alone the backward kernel is 17 % faster (122 -> 101 us) and the forward 18 % slower (46 -> 54 us),
-        # but in this two-stream step the extra 0.76 GB of traffic per iteration costs more than the vector work it saves
-        # (1.917 -> 1.944 ms with every network keeping them, 1.915 with the lattice branch alone): off by default
-        self.keep_h = self.keep_h_lat = bool(keep_hidden)
-        hbuf = lambda n_slots, s: f(s[3] * n_slots * s[2]) if self.keep_h else None
-        self.h_c, self.h_f, self.h_col, self.h_log = hbuf(P, self.shp_c), hbuf(self.n_slots, self.shp_f), hbuf(P, self.shp_col), hbuf(P, self.shp_log)
+        self.ws_mlp1 = [self.ws_mlp] * 4
         self.scatter_form, self.scatter_cap = ops.SCATTER_FORM
         enc_ws = lambda n: f(max(int(raw_lib.dns_encode_bwd_ws_floats(n, C.byref(self.meta.c), self.scatter_form, self.scatter_cap)), 4))
         self.ws_enc = enc_ws(P)
@@ -343,13 +323,8 @@ class MapStep:
             lhi = min(lb + 1, n)                                          # + the next slab's first plane (halo: closes the x-differences)
             self.lat_nx, self.lat_halo = lhi - la, 1 if lhi > lb else 0
             Pl = self.Pl = self.lat_nx * n * n
-            self.bufl, self.occ, self.d_occ, self.d_bufl = f(Pl, ld), f(Pl, 1), f(Pl, 1), f(Pl, ld)
-            if self.half:
-                self.xhl = torch.empty(Pl, ld, device=dev, dtype=torch.float16)
-            if self.sr:
-                np_ = self.sr_planes
-                self.xsl, self.xexpl = torch.empty(Pl, np_ * ld, device=dev, dtype=torch.float16), torch.empty(Pl, device=dev, dtype=torch.int32)
-                self.rows_l = DnsSplitRows(self.xsl.data_ptr(), self.xexpl.data_ptr(), np_ * ld, ld if np_ == 2 else 0)
+            self.lat_rows = new_rows(Pl, 0)
+            self.occ, self.d_occ, self.d_bufl = f(Pl, 1), f(Pl, 1), f(Pl, ld)
             self.pts_l = f(Pl, 3)
             # Row m of the lattice branch's buffers holds lattice element lat_order[m], the elements in MORTON order of (i, j, k):
             # neighbouring rows then share hash-table lines and the lattice's encoding kernel runs 2.3x faster (112 -> 49 us at
@@ -379,7 +354,10 @@ class MapStep:
             # up the slabs of one lattice
             self.w_sm = torch.full((1,), m.lambda_sm if self.union else m.lambda_sm / self.world, device=dev)
             self.ws_mlp_l = mlp_ws(Pl, self.shp_c)
-            self.h_l = f(self.shp_c[3] * Pl * self.shp_c[2]) if self.keep_h_lat else None
+            # the lattice runs the occupancy row only.  (Its points carry no pose: only the grid columns' input gradient has a
+            # consumer, the table scatter -- DNS_MLP_DX_FROM, which the saved-activation backward does not take)
+            self.net_occ = net(self.p_coarse, self.shp_c, 1, hidden=hbuf(Pl, self.shp_c))
+            self.acc_occ = ops.MLP_DX_FROM(self.pe_dim) if self.net_occ.hidden is None else 0
             self.ws_enc_l = enc_ws(Pl)
         if getattr(m, "_side_stream", None) is None:
             m._side_stream = torch.cuda.Stream(device=dev)
@@ -389,43 +367,19 @@ class MapStep:
     # ------------------------------------------------------------------------------------------------------------------
     def _prepare_weights(self, st):
         """The step's operand images from the CURRENT weights (after the last Adam step): five small launches."""
-        for prm, n_in, n_out, nn, nl, n_sets, stride, view, lv, _ in self._prep_jobs:
+        for prm, n_in, n_out, nn, nl, n_sets, stride, view, lv in self._prep_jobs:
             check(ops.lib.dns_mlp_prepare(ptr(prm), n_in, n_out, nn, nl, n_sets, stride, ptr(view), lv, st), "dns_mlp_prepare")
-
-    def _w(self, params, n_out):
-        """(pointer, flag) of a network's weights for an MLP launch: its prepared images, or the fp32 parameters."""
-        blob = self._blobs.get((params.data_ptr(), n_out)) if self.use_prep else None
-        if blob is None:
-            return ptr(params), 0
-        return ptr(blob), ops.MLP_PREPARED_FLAG
 
     def _lattice_branch(self, cur, st):
         """Forward and backward of the smoothness term on the side stream: its loss weight is a constant, so its backward
         needs nothing from the ray branch."""
-        lib = ops.lib
-        Pl, ld, pe = self.Pl, self.ld, self.pe_dim
-        pts = self.pts_l
+        lib, rows = ops.lib, self.lat_rows
+        Pl, ld, pts = self.Pl, self.ld, self.pts_l
         check(lib.dns_lattice_points(ptr(cur.draws["r6"]), self.lat_consts, self.n_lat, ptr(self.lat_order), Pl, ptr(pts), st),
               "dns_lattice_points")
         meta = C.byref(self.meta.c)
-        grid_l = _V(self.bufl.data_ptr() + 4 * pe)
-        n_in, _, nn, nl = self.shp_c
-        if self.half:
-            check(lib.dns_encode_fwd_split(ptr(pts), None, Pl, self.n_bins, ptr(self.p_table), meta, None, None, 0, ptr(self.xhl), ld,
-                                           None, ops.SPLIT_PLAIN, None, st), "dns_encode_fwd_split")
-            check(lib.dns_mlp_fwd_half(ptr(self.xhl), ld, None, 0, 0, ptr(self.p_coarse), n_in, 1, nn, nl, ptr(self.occ), 1, Pl,
-                                       None, None, 0, 0, st), "dns_mlp_fwd_half")
-        elif self.sr:
-            check(lib.dns_encode_fwd_split(ptr(pts), None, Pl, self.n_bins, ptr(self.p_table), meta, None, ptr(self.bufl), ld,
-                                           ptr(self.xsl), self.sr_planes * ld, ptr(self.xexpl), self.sr_flags, None, st), "dns_encode_fwd_split")
-            check(lib.dns_mlp_fwd_split(C.byref(self.rows_l), None, 0, ptr(self.p_coarse), n_in, 1, nn, nl, ptr(self.occ), 1, Pl,
-                                        None, None, 0, self.fp16, st), "dns_mlp_fwd_split")
-        else:
-            check(lib.dns_encode_fwd(ptr(pts), None, Pl, self.n_bins, ptr(self.p_table), meta, None, ptr(self.bufl), ld,
-                                     grid_l, ld, None, st), "dns_encode_fwd")
-            wl, wflag = self._w(self.p_coarse, 1)
-            check(lib.dns_mlp_fwd(ptr(self.bufl), ld, None, 0, 0, wl, n_in, 1, nn, nl, ptr(self.occ), 1, Pl,
-                                  None, None, 0, ptr(self.h_l), self.fp16 | wflag, st), "dns_mlp_fwd")
+        rows.encode(pts, None, self.n_bins, self.p_table, meta, None, None, st)
+        rows.fwd(self.net_occ, self.occ, st)
         # the branch runs in MORTON order of the lattice elements (see __init__); the TV kernels want the x-major cube: two 1 MB
         # permutations (the network's occupancy out, its gradient back in)
         torch.index_select(self.occ, 0, self.lat_slot, out=self.occ_x)
@@ -433,24 +387,8 @@ class MapStep:
         check(lib.dns_tv_bwd(ptr(self.occ_x), 1, self.lat_nx, self.n_lat, self.lat_halo, self.sp, ptr(self.w_sm), ptr(self.d_occ_x), st),
               "dns_tv_bwd")
         torch.index_select(self.d_occ_x, 0, self.lat_order_l, out=self.d_occ)
-        if self.half:
-            # (the lattice points carry no pose: only the grid columns' input gradient has a consumer, the table scatter)
-            check(lib.dns_mlp_bwd_half(ptr(self.xhl), ld, None, 0, 0, ptr(self.d_occ), 1, ptr(self.p_coarse), n_in, 1, nn, nl,
-                                       ptr(self.d_bufl), ld, None, 0, ptr(cur.g_coarse), Pl, None, None, 0, ops.MLP_DX_FROM(pe),
-                                       self.loss_scale, st), "dns_mlp_bwd_half")
-        elif self.sr:
-            check(lib.dns_mlp_bwd_split(C.byref(self.rows_l), None, 0, ptr(self.d_occ), 1, ptr(self.p_coarse), n_in, 1, nn, nl,
-                                        ptr(self.d_bufl), ld, None, 0, ptr(cur.g_coarse), ptr(self.ws_mlp_l), Pl, None, None, 0,
-                                        self.fp16, st), "dns_mlp_bwd_split")
-            check(lib.dns_mlp_dwin(ptr(self.bufl), ld, None, 0, 0, n_in, nn, nl, ptr(cur.g_coarse), ptr(self.ws_mlp_l), Pl, None, None,
-                                   0, self.fp16, st), "dns_mlp_dwin")
-        else:
-            # (the lattice points carry no pose: only the grid columns' input gradient has a consumer, the table scatter)
-            wl, wflag = self._w(self.p_coarse, 1)
-            check(lib.dns_mlp_bwd(ptr(self.bufl), ld, None, 0, 0, ptr(self.d_occ), 1, wl, n_in, 1, nn, nl,
-                                  ptr(self.d_bufl), ld, None, 0, ptr(cur.g_coarse), ptr(self.ws_mlp_l), Pl, None, None, 0, ptr(self.h_l),
-                                  self.fp16 | wflag | (0 if self.h_l is not None else ops.MLP_DX_FROM(pe)), st), "dns_mlp_bwd")
-        d_grid_l = _V(self.d_bufl.data_ptr() + 4 * pe)
+        rows.bwd(self.net_occ, self.d_occ, self.d_bufl, None, cur.g_coarse, self.ws_mlp_l, self.acc_occ, st)
+        d_grid_l = _V(self.d_bufl.data_ptr() + 4 * self.pe_dim)
         check(lib.dns_encode_bwd(ptr(pts), None, Pl, self.n_bins, ptr(self.p_table), meta, None, ld, d_grid_l, ld,
                                  ptr(cur.g_table), None, None, ptr(self.ws_enc_l), self.scatter_form, self.scatter_cap, st),
               "dns_encode_bwd")
@@ -582,76 +520,27 @@ class MapStep:
                                     ptr(self.pts), st), "dns_raygen_sample")
         # ---- encoding (slams/mapping.py:608 + models/decoder.py:45-48)
         meta = C.byref(self.meta.c)
-        grid = _V(self.buf.data_ptr() + 4 * pe)
-        sr = self.sr
-        half = self.half
-        if half:
-            check(lib.dns_encode_fwd_split(ptr(self.pts), self.b6, P, self.n_bins, ptr(self.p_table), meta, ptr(self.x3), None, 0,
-                                           ptr(self.xh), ld, None, ops.SPLIT_PLAIN, ptr(self.dydx), st), "dns_encode_fwd_split")
-        elif sr:
-            check(lib.dns_encode_fwd_split(ptr(self.pts), self.b6, P, self.n_bins, ptr(self.p_table), meta, ptr(self.x3), ptr(self.buf),
-                                           ld, ptr(self.xs), self.sr_planes * ld, ptr(self.xexp), self.sr_flags, ptr(self.dydx), st),
-                  "dns_encode_fwd_split")
-        else:
-            check(lib.dns_encode_fwd(ptr(self.pts), self.b6, P, self.n_bins, ptr(self.p_table), meta, ptr(self.x3), ptr(self.buf),
-                                     ld, grid, ld, ptr(self.dydx), st), "dns_encode_fwd")
+        rows = self.rows
+        rows.encode(self.pts, self.b6, self.n_bins, self.p_table, meta, self.x3, self.dydx, st)
         # ---- the 2-D branch inside the iteration (slams/mapping.py:532-551): reference poses -> projected image code + relative
         # point -> OneBlob -> Merge network; its mean over the views is taken by the feature block below
+        code, views = self.features, None
         if self.stem:
-            R, Pf = self.R, self.Pf
-            n_in_m, n_out_m, nn_m, nl_m = self.shp_m
-            check(lib.dns_refer_poses(ptr(self.Q), ptr(self.T), ptr(self.ref_src), ptr(self.ref_fixed), K * R, ptr(self.w2c),
+            s2 = self.stem2d
+            check(lib.dns_refer_poses(ptr(self.Q), ptr(self.T), ptr(self.ref_src), ptr(self.ref_fixed), K * self.R, ptr(self.w2c),
                                       ptr(self.origin), st), "dns_refer_poses")
-            check(lib.dns_feature_gather_frames(ptr(self.pts), ptr(self.w2c), ptr(self.origin), self.K9, ptr(self.feat_maps), K, R, Pf,
-                                                self.Cs, self.fh, self.fw, H, W, _V(self.mbuf.data_ptr() + 4 * self.pe_m), n_in_m,
-                                                ptr(self.rel), st), "dns_feature_gather_frames")
-            check(lib.dns_encode_fwd(ptr(self.rel), self.b6m, self.Mr, self.n_bins_m, None, None, ptr(self.xm), ptr(self.mbuf), n_in_m,
-                                     None, 0, None, st), "dns_encode_fwd")
-            check(lib.dns_mlp_fwd(ptr(self.mbuf), n_in_m, None, 0, 0, ptr(self.p_merge), n_in_m, n_out_m, nn_m, nl_m, ptr(self.mlat),
-                                  n_out_m, self.Mr, None, None, 0, None, self.fp16, st), "dns_mlp_fwd")
+            s2.forward(self.pts, self.w2c, self.origin, self.feat_maps, H, W, self.net_m, st)
+            code, views = s2.mlat, (self.R, self.Pf)
         # ---- the four networks (slams/mapping.py:616-626)
-        fp16 = self.fp16
-        rows_x = C.byref(self.rows_x) if sr else None
-        rows_f = C.byref(self.rows_f) if sr else None
-
-        def fwd(x2, n_in1, params, shape, y, ri, tg, n_slots, stride, hs):
-            n_in, n_out, nn, nl = shape
-            if half:                                   # x2: the f16 feature block (self.feath) where the fp32 paths take self.feat
-                check(lib.dns_mlp_fwd_half(ptr(self.xh), ld, None if x2 is None else ptr(self.feath), self.n_feat, n_in1, ptr(params),
-                                           n_in, n_out, nn, nl, ptr(y), y.stride(0), n_slots, ptr(ri), ptr(tg), stride,
-                                           0 if x2 is None else self.live, st), "dns_mlp_fwd_half")
-                return
-            if sr:
-                check(lib.dns_mlp_fwd_split(rows_x, None if x2 is None else rows_f, n_in1, ptr(params), n_in, n_out, nn, nl, ptr(y),
-                                            y.stride(0), n_slots, ptr(ri), ptr(tg), stride, fp16, st), "dns_mlp_fwd_split")
-                return
-            wp, wflag = self._w(params, n_out)
-            check(lib.dns_mlp_fwd(ptr(self.buf), ld, ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, wp, n_in, n_out,
-                                  nn, nl, ptr(y), y.stride(0), n_slots, ptr(ri), ptr(tg), stride, ptr(hs),
-                                  fp16 | wflag | (0 if x2 is None else self.live), st), "dns_mlp_fwd")
-
         if prep_ev is not None:
             main.wait_event(prep_ev)                   # the operand images of this step (side stream)
-        fwd(None, 0, self.p_coarse, self.shp_c, self.coarse, None, None, P, 0, self.h_c)
-        fine, row_index, tile_group = cur.fine, cur.row_index, cur.tile_group     # zeroed / routed by _prepare
-        fwd(None, 0, self.p_pool, self.shp_f, fine, row_index, tile_group, self.n_slots, self.p_pool.shape[-1], self.h_f)
+        rows.fwd(self.net_c, self.coarse, st)
+        fine = cur.fine                                # zeroed / routed by _prepare
+        rows.fwd(cur.net_pool, fine, st)
         # (latents | truncated 2-D code) for the colour / logit networks, occupancy into the compositing input (:553-556, :622-627)
-        if half:
-            check(lib.dns_feature_block_split(ptr(fine), self.hid + 1, self.hid, ptr(self.features), self.n_feat - self.hid, 1, 0,
-                                              ptr(self.z), ptr(self.gt_depth), N, S, None, 0, ptr(self.feath), self.n_feat, None,
-                                              ops.SPLIT_PLAIN, ptr(self.raw), st), "dns_feature_block_split")
-        elif sr or self.stem:
-            code, n_ref, Pf_ = (self.mlat, self.R, self.Pf) if self.stem else (self.features, 1, 0)
-            check(lib.dns_feature_block_split(ptr(fine), self.hid + 1, self.hid, ptr(code), self.n_feat - self.hid, n_ref, Pf_,
-                                              ptr(self.z), ptr(self.gt_depth), N, S, ptr(self.feat), self.n_feat,
-                                              ptr(self.fxs) if sr else None, self.sr_planes * self.n_feat,
-                                              ptr(self.fexp) if sr else None, self.sr_flags, ptr(self.raw), st),
-                  "dns_feature_block_split")
-        else:
-            check(lib.dns_feature_block(ptr(fine), self.hid + 1, self.hid, ptr(self.features), self.n_feat - self.hid, ptr(self.z),
-                                        ptr(self.gt_depth), N, S, ptr(self.feat), self.n_feat, ptr(self.raw), st), "dns_feature_block")
-        fwd(self.feat, pe, self.p_color, self.shp_col, self.raw, None, None, P, 0, self.h_col)
-        fwd(self.feat, pe, self.p_logit, self.shp_log, self.logit, None, None, P, 0, self.h_log)
+        rows.feature_block(fine, self.hid, code, views, self.z, self.gt_depth, N, S, self.raw, st)
+        rows.fwd(self.net_col, self.raw, st, True)
+        rows.fwd(self.net_log, self.logit, st, True)
         # ---- compositing + losses (utils/common.py:506-537, slams/mapping.py:887-907).  raw[:, 0:3] stays the colour network's
         # LOGITS: the compositing kernels apply the sigmoid (models/decoder.py:124) on the fly, forward and backward
         Cn, L = self.n_class, self.hid + 1
@@ -664,15 +553,13 @@ class MapStep:
                                 ptr(self.gt_depth), ptr(self.gt_label), ptr(self.inside), ptr(fine), ptr(self.coarse),
                                 ptr(self.z), ptr(self.sums_ws), st), "dns_loss_sums")
         if self.dist_on:
+            import torch.distributed as dist
             m.dist.allreduce_sums(self.sums_ws[:16])
         # (the finalize runs inside the rays' backward kernel below: dns_loss_finalize_bwd)
 
-        # ---- backward.  d_featx [P, 4 + n_feat]: column 3 = d occupancy, columns 4.. = the feature-block gradient of the colour /
-        # logit networks, so columns 3 .. 3 + L are the fine network's output gradient in one strided view.  The losses write
-        # their d_fine THERE, compositing adds d occupancy, the colour and logit networks add (+=) their feature gradients: no
-        # [P, L] sum kernel.  (The 2-D code's columns only ever accumulate; nothing reads them -- the code has no gradient.)
+        # ---- backward.  The losses write their d_fine into d_featx (launch.alloc_ray_buffers), compositing adds d occupancy, the
+        # colour and logit networks add (+=) their feature gradients: no [P, L] sum kernel.
         ldf = 4 + self.n_feat
-        d_fine_dst = _V(self.d_featx.data_ptr() + 4 * 3)
         # ray losses -> compositing (its d_raw[:, 0:3] IS the colour network's output gradient: the sigmoid's backward is folded
         # in) -> point losses, which also add the compositing's d occupancy (d_raw[:, 3]) into column 0 of d_fine
         check(lib.dns_loss_finalize_bwd(lam, N, S, Cn, L, 0, ptr(self.sums_ws), ptr(self.out), ptr(self.one), ptr(self.rgb),
@@ -683,89 +570,37 @@ class MapStep:
                                        ptr(self.d_color), None, ptr(self.d_sem), ptr(self.d_raw), ptr(self.d_logit), 1, st),
               "dns_composite_bwd_ex")
         check(lib.dns_loss_bwd_points(lam, N, S, Cn, L, ptr(self.out), ptr(self.one), ptr(self.gt_depth), ptr(self.inside), ptr(fine),
-                                      ptr(self.coarse), ptr(self.z), d_fine_dst, ptr(self.d_coarse), ldf,
+                                      ptr(self.coarse), ptr(self.z), ptr(self.d_fine), ptr(self.d_coarse), ldf,
                                       _V(self.d_raw.data_ptr() + 12), 4, st), "dns_loss_bwd_points")
 
         # dW_in of every network on the SIDE stream (2.02 -> 1.90 ms per step): the streaming kernel is memory-bound and needs only
         # what its backward kernel left in the workspace, the next network's backward kernel is vector-bound -- the pair fills the
-        # machine where either alone does not
-        fork_dwin = on_side and not half               # (half rows: dW_in is formed inside the ONE backward kernel)
-        side_st = _V(self.side.cuda_stream)
-        nws = [0]
-
-        def bwd(x2, n_in1, dy, params, shape, d_x2, d_p, ri, tg, n_slots, stride, acc, hs):
-            n_in, n_out, nn, nl = shape
-            live = 0 if x2 is None else self.live
-            ws = self.ws_mlp4[nws[0]] if fork_dwin else self.ws_mlp
-            nws[0] += 1
-            if half:
-                check(lib.dns_mlp_bwd_half(ptr(self.xh), ld, None if x2 is None else ptr(self.feath), self.n_feat, n_in1, ptr(dy),
-                                           dy.stride(0), ptr(params), n_in, n_out, nn, nl, ptr(self.d_buf), ld, ptr(d_x2),
-                                           0 if d_x2 is None else d_x2.stride(0), ptr(d_p), n_slots, ptr(ri), ptr(tg), stride,
-                                           acc | live, self.loss_scale, st), "dns_mlp_bwd_half")
-                return
-            if sr:
-                check(lib.dns_mlp_bwd_split(rows_x, None if x2 is None else rows_f, n_in1, ptr(dy), dy.stride(0), ptr(params), n_in,
-                                            n_out, nn, nl, ptr(self.d_buf), ld, ptr(d_x2), 0 if d_x2 is None else d_x2.stride(0),
-                                            ptr(d_p), ptr(ws), n_slots, ptr(ri), ptr(tg), stride, acc | fp16, st), "dns_mlp_bwd_split")
-                if not fork_dwin:
-                    check(lib.dns_mlp_dwin(ptr(self.buf), ld, ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, n_in, nn, nl, ptr(d_p),
-                                           ptr(ws), n_slots, ptr(ri), ptr(tg), stride, fp16 | live, st), "dns_mlp_dwin")
-            else:
-                wp, wflag = self._w(params, n_out)
-                check(lib.dns_mlp_bwd(ptr(self.buf), ld, ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(dy), dy.stride(0),
-                                      wp, n_in, n_out, nn, nl, ptr(self.d_buf), ld, ptr(d_x2),
-                                      0 if d_x2 is None else d_x2.stride(0), ptr(d_p), ptr(ws), n_slots, ptr(ri), ptr(tg),
-                                      stride, ptr(hs), acc | fp16 | wflag | live | (ops.MLP_NO_DWIN_FLAG if fork_dwin else 0), st), "dns_mlp_bwd")
-            if fork_dwin:
-                # dW_in = dH_1^T x (memory-bound, needs only what this launch left in ws) on the side stream, beside the next
-                # network's vector-bound backward kernel
-                ev = torch.cuda.Event()
-                ev.record(main)
-                self.side.wait_event(ev)
-                with torch.cuda.stream(self.side):
-                    check(lib.dns_mlp_dwin(ptr(self.buf), ld, ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, n_in, nn, nl, ptr(d_p),
-                                           ptr(ws), n_slots, ptr(ri), ptr(tg), stride, fp16 | live, side_st), "dns_mlp_dwin")
-
-        d_feat = self.d_featx[:, 4:]
-        bwd(None, 0, self.d_coarse, self.p_coarse, self.shp_c, None, cur.g_coarse, None, None, P, 0, 0, self.h_c)
-        bwd(self.feat, pe, self.d_raw, self.p_color, self.shp_col, d_feat, cur.g_color, None, None, P, 0, 3, self.h_col)
-        bwd(self.feat, pe, self.d_logit, self.p_logit, self.shp_log, d_feat, cur.g_logit, None, None, P, 0, 3, self.h_log)
+        # machine where either alone does not.  (Not where the ONE backward kernel forms dW_in itself: half rows.)
+        fork = (main, self.side, _V(self.side.cuda_stream)) if on_side and rows.forks_dwin else None
+        ws = self.ws_mlp4 if fork else self.ws_mlp1    # one workspace per network when dW_in is forked
+        d_buf, d_feat = self.d_buf, self.d_feat
+        rows.bwd(self.net_c, self.d_coarse, d_buf, None, cur.g_coarse, ws[0], 0, st, fork)
+        rows.bwd(self.net_col, self.d_raw, d_buf, d_feat, cur.g_color, ws[1], 3, st, fork)
+        rows.bwd(self.net_log, self.d_logit, d_buf, d_feat, cur.g_logit, ws[2], 3, st, fork)
         if self.stem:
-            # Merge's backward (models/decoder.py:67-77): d code -> the R views' latent gradients -> weight gradients and, under
-            # bundle adjustment, d OneBlob -> d(relative point) (added to the points' gradient before the pose reduction)
-            n_in_m, n_out_m, nn_m, nl_m = self.shp_m
-            pe_m = self.pe_m
-            check(lib.dns_merge_dy(_V(self.d_featx.data_ptr() + 4 * (4 + self.hid)), ldf, n_out_m, self.R, self.Pf, ptr(self.z),
-                                   ptr(self.gt_depth), N, S, ptr(self.mdy), st), "dns_merge_dy")
-            check(lib.dns_mlp_bwd(ptr(self.mbuf), n_in_m, _V(self.mbuf.data_ptr() + 4 * pe_m), n_in_m, pe_m, ptr(self.mdy), n_out_m,
-                                  ptr(self.p_merge), n_in_m, n_out_m, nn_m, nl_m, ptr(self.d_mpe), pe_m, None, 0, ptr(cur.g_merge),
-                                  ptr(self.ws_m), self.Mr, None, None, 0, None,
-                                  ops.MLP_DX_FIRST_FLAG | fp16 | (ops.MLP_NO_DWIN_FLAG if fork_dwin else 0), st), "dns_mlp_bwd")
-            if fork_dwin:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                self.side.wait_event(ev)
-                with torch.cuda.stream(self.side):
-                    check(lib.dns_mlp_dwin(ptr(self.mbuf), n_in_m, None, 0, 0, n_in_m, nn_m, nl_m, ptr(cur.g_merge), ptr(self.ws_m),
-                                           self.Mr, None, None, 0, fp16, side_st), "dns_mlp_dwin")
-            if self.is_BA:
-                check(lib.dns_encode_bwd(ptr(self.xm), self.b6m, self.Mr, self.n_bins_m, None, None, ptr(self.d_mpe), pe_m, None, 0,
-                                         None, ptr(self.d_rel), None, None, 0, 0, st), "dns_encode_bwd")
-        bwd(None, 0, self.d_featx[:, 3:3 + L], self.p_pool, self.shp_f, None, cur.g_pool, row_index, tile_group,
-            self.n_slots, self.p_pool.shape[-1], 1, self.h_f)
+            s2.backward(_V(self.d_featx.data_ptr() + 4 * (4 + self.hid)), ldf, self.z, self.gt_depth, N, S, self.net_m, cur.g_merge,
+                        st, fork)
+        rows.bwd(cur.net_pool, self.d_fine, d_buf, None, cur.g_pool, ws[3], 1, st, fork)
         work = None
         if self.dist_on:
             # colour | logit | pool gradients are complete once the LAST forked dW_in has run: with the fork the all-reduce is
             # issued from the side stream (behind that kernel, which itself waited for the fine network's backward kernel)
-            import torch.distributed as dist
-            if fork_dwin:
-                with torch.cuda.stream(self.side):
-                    work = dist.all_reduce(cur.G_early, op=dist.ReduceOp.SUM, group=m.dist.group, async_op=True)
-            else:
+            with torch.cuda.stream(self.side if fork else main):
                 work = dist.all_reduce(cur.G_early, op=dist.ReduceOp.SUM, group=m.dist.group, async_op=True)
         d_grid = _V(self.d_buf.data_ptr() + 4 * pe)
         fork_pose = self.is_BA and on_side
+
+        def pose_grad(s_):                             # d(points) -> d(quat, trans) of every frame
+            if self.stem:
+                s2.add_ref_sum(P, self.d_x3, s_)
+            check(lib.dns_raygen_bwd(ptr(pix), ptr(self.Q), self.camv, 0, H, 0, W, K, npf, S, ptr(self.z), ptr(self.d_x3), None,
+                                     None, ptr(self.ray_ws), ptr(cur.g_quat), ptr(cur.g_trans), s_), "dns_raygen_bwd")
+
         if fork_pose:
             # the pose gradient (a streaming kernel over the saved d(features)/dx, then the tiny pose reduction) on the side
             # stream beside the table scatter (vector-bound): 2.036-2.063 -> 2.027-2.047 ms per step
@@ -774,22 +609,15 @@ class MapStep:
                 st2 = _V(self.side.cuda_stream)
                 check(lib.dns_encode_bwd(ptr(self.x3), self.b6, P, self.n_bins, ptr(self.p_table), meta, ptr(self.d_buf), ld, d_grid,
                                          ld, None, ptr(self.d_x3), ptr(self.dydx), None, 0, 0, st2), "dns_encode_bwd")
-                if self.stem:
-                    check(lib.dns_add_ref_sum(ptr(self.d_rel), self.R, self.Pf, P, ptr(self.d_x3), st2), "dns_add_ref_sum")
-                check(lib.dns_raygen_bwd(ptr(pix), ptr(self.Q), self.camv, 0, H, 0, W, K, npf, S, ptr(self.z), ptr(self.d_x3), None,
-                                         None, ptr(self.ray_ws), ptr(cur.g_quat), ptr(cur.g_trans), st2), "dns_raygen_bwd")
+                pose_grad(st2)
         check(lib.dns_encode_bwd(ptr(self.x3), self.b6, P, self.n_bins, ptr(self.p_table), meta, ptr(self.d_buf), ld, d_grid, ld,
                                  ptr(cur.g_table), ptr(self.d_x3) if (self.is_BA and not fork_pose) else None, ptr(self.dydx),
                                  ptr(self.ws_enc), self.scatter_form, self.scatter_cap, st), "dns_encode_bwd")
         if self.is_BA and not fork_pose:
-            if self.stem:
-                check(lib.dns_add_ref_sum(ptr(self.d_rel), self.R, self.Pf, P, ptr(self.d_x3), st), "dns_add_ref_sum")
-            check(lib.dns_raygen_bwd(ptr(pix), ptr(self.Q), self.camv, 0, H, 0, W, K, npf, S, ptr(self.z), ptr(self.d_x3), None,
-                                     None, ptr(self.ray_ws), ptr(cur.g_quat), ptr(cur.g_trans), st), "dns_raygen_bwd")
+            pose_grad(st)
         if on_side:
             main.wait_stream(self.side)
         if self.dist_on:
-            import torch.distributed as dist
             work2 = dist.all_reduce(cur.G_late, op=dist.ReduceOp.SUM, group=m.dist.group, async_op=True)
             work.wait()
             work2.wait()
@@ -851,24 +679,12 @@ class TrackStep:
         dev = self.dev = torch.device(t.device)
         if dev.type != "cuda":
             raise ValueError("dns_slam_amd ops run on the GPU only; there is no CPU fallback")
-        # features: None | per-sample code [N, S, C] | stem maps [1, n_refer, C, h, w] + refer_frames['est_w2c'] [n_refer, 4, 4]:
-        # then feature_matching + Decoder.merge run inside every iteration (slams/tracking.py:162-165), Merge frozen like the scene
-        self.stem = features is not None and features.dim() == 5
-        if features is not None and features.dim() not in (3, 5):
-            raise ValueError("TrackStep: features is the per-sample code [N, S, C] or the stem feature maps [1, R, C, h, w]")
-        if self.stem and refer_frames is None:
-            raise ValueError("TrackStep: stem feature maps need refer_frames['est_w2c']")
+        # (stem maps [1, n_refer, C, h, w] + refer_frames['est_w2c'] [n_refer, 4, 4]: slams/tracking.py:162-165, Merge frozen like the scene)
         dec = t.decoder
+        _read_scene(self, "TrackStep", dec, features, refer_frames, "[1, R, C, h, w]", "refer_frames['est_w2c']")
         self.prep = t.prepare_frame(cur_frames)
-        self.features = None if (features is None or self.stem) else features.to(dev).float().contiguous()
         self.betas, self.eps = betas, eps
         self.pe_dim, self.grid_dim, self.hid = dec.pe_dim, dec.grid_dim, dec.hidden_dim
-        nets = (dec.coarse_fn.decoder, dec.out_fn.color_decoder, dec.out_fn.logit_decoder)
-        self.fp16 = ops.MLP_FP16_FLAG if getattr(nets[0], "fp16", False) else 0
-        shp = lambda n: (n.n_input_dims, n.n_output_dims, n.n_neurons, n.n_hidden_layers)
-        self.shp_c, self.shp_col, self.shp_log = (shp(n) for n in nets)
-        self.p_coarse, self.p_color, self.p_logit = (n.params for n in nets)
-        self.p_table, self.meta, self.n_bins = dec.pe_fn.grid_fn.params, dec.pe_fn.grid_fn.meta, dec.pe_fn.pe_fn.n_bins
         self.n_feat = self.hid + (self.hid if (features is None or self.stem) else self.features.shape[-1])
         if not (self.pe_dim % 4 == 0 and self.pe_dim <= 64 and self.n_feat <= 64 and self.n_feat % 4 == 0
                 and self.shp_col[0] == self.pe_dim + self.n_feat and self.shp_c[1] == self.hid + 1):
@@ -896,49 +712,29 @@ class TrackStep:
             it.p, it.g, it.m, it.v, it.n, it.lr = p.data_ptr(), g.data_ptr(), self.M.data_ptr() + 4 * o, self.V.data_ptr() + 4 * o, n, l
         self.best_loss = torch.full((1,), float("inf"), device=dev)
         self.best_cam = torch.cat((self.Q.reshape(-1), self.T.reshape(-1))).clone()
-        self.rays_o, self.rays_d, self.gt_color, self.gt_depth = f(N, 3), f(N, 3), f(N, 3), f(N)
-        self.gt_label = torch.empty(N, device=dev, dtype=torch.int64)
-        self.inside, self.valid = torch.empty(N, device=dev, dtype=torch.uint8), torch.empty(N, device=dev, dtype=torch.uint8)
-        self.z, self.pts = f(N, S), f(N, S, 3)
+        alloc_ray_buffers(self, N, S, self.n_class, self.n_feat, dev)
+        self.valid = torch.empty(N, device=dev, dtype=torch.uint8)
         self.dmax_ws = torch.empty(1, device=dev, dtype=torch.int32)
-        self.x3, self.buf = f(P, 3), f(P, ld)
+        rows = self.rows = Fp32Rows(P, ld, self.pe_dim, self.n_feat, dev)
+        self.buf, self.feat = rows.buf, rows.feat
         self.dydx = f(self.meta.n_levels * 3 * P * 2)
-        nf = self.hid + 1
-        self.lat, self.feat = f(P, nf), f(P, self.n_feat)
-        self.raw, self.logit = f(P, 4), f(P, self.n_class)
-        self.depth, self.var, self.rgb, self.weights, self.sem = f(N), f(N), f(N, 3), f(N, S), f(N, self.n_class)
-        self.sums_ws, self.out, self.one = f(ops.LOSS_SUMS_FLOATS), f(16), torch.ones(1, device=dev)
-        self.d_color, self.d_depth, self.d_var, self.d_sem = f(N, 3), f(N), f(N), f(N, self.n_class)
-        self.d_raw, self.d_logit, self.d_col = f(P, 4), f(P, self.n_class), f(P, 4)
-        self.d_featx = torch.zeros(P, 4 + self.n_feat, device=dev)
-        self.d_x3 = f(P, 3)
+        self.lat = f(P, self.hid + 1)
+        self.d_lat = self.d_featx[:, 3:3 + self.hid + 1]               # the coarse network's output gradient (see alloc_ray_buffers)
+        self.d_var, self.d_col = f(N), f(P, 4)
         raw_lib = ops.lib._raw
         if self.stem:
             _, R, Cs, fh, fw = features.shape
-            self.R, self.Cs, self.fh, self.fw = int(R), int(Cs), int(fh), int(fw)
-            self.feat_maps = features.detach().to(dev).float()[0].permute(0, 2, 3, 1).contiguous()
-            mg = dec.merge.decoder
-            self.shp_m, self.p_merge = shp(mg), mg.params
-            self.n_bins_m = dec.merge.pe_fn.n_bins
-            self.pe_m = 3 * self.n_bins_m
-            if not (self.shp_m[0] == self.pe_m + Cs and self.shp_m[1] == self.hid and self.pe_m % 4 == 0):
-                raise ValueError("TrackStep: Decoder.merge's network does not match the stem features / hidden width")
-            self.b6m = ops._bound6(dec.merge.bound)
-            w2c = refer_frames["est_w2c"].clone().detach().to(dev).float()                 # slams/tracking.py:162
-            self.w2c = w2c.reshape(R, 16).contiguous()
-            self.origin = torch.inverse(w2c)[:, :3, 3].contiguous()                          # utils/common.py:672-674
-            Mr = self.Mr = R * P
-            self.mbuf, self.rel, self.xm = f(Mr, self.shp_m[0]), f(Mr, 3), f(Mr, 3)
-            self.mlat, self.mdy = f(Mr, self.hid), f(Mr, self.hid)
-            self.d_mpe, self.d_rel = f(Mr, self.pe_m), f(Mr, 3)
-            self.K9 = (C.c_float * 9)(float(t.fx), 0.0, float(t.cx), 0.0, float(t.fy), float(t.cy), 0.0, 0.0, 1.0)
+            self.R = int(R)
+            self.stem2d = Stem2D("TrackStep", dec.merge, 1, R, P, Cs, fh, fw, self.hid, (t.fx, t.fy, t.cx, t.cy), dev,
+                                 want_dw=False, want_pose=True)
+            self.feat_maps, self.w2c, self.origin = f(R, fh, fw, Cs), f(R, 16), f(R, 3)
+            self._set_views(features, refer_frames)
         self.ray_ws = f(max(int(raw_lib.dns_raygen_bwd_ws_floats(1, N)), 1))
         # The scene is frozen for the whole loop: its networks' operand images are built ONCE (DNS_MLP_PREPARED) and every
         # launch copies them in instead of rebuilding them per workgroup (0.253 -> 0.245 ms per iteration).  MapStep does not
         # use this: its weights change every step, and in the two-stream step the five extra launches plus the copy-in traffic
         # cost more than the per-workgroup rebuild (measured on one box: 2.105 without, 2.111 with the images but no
         # re-preparation, 2.133 with both; stand-alone the prepared launches are 1-3 us (forward) and 4-7 us (backward) faster).
-        self.PREP = ops.MLP_PREPARED_FLAG
         nets_w = [(self.p_coarse, self.shp_c), (self.p_color, self.shp_col), (self.p_logit, self.shp_log)]
         if self.stem:
             nets_w.append((self.p_merge, self.shp_m))
@@ -948,6 +744,9 @@ class TrackStep:
         self.g = None                                      # the captured iteration (run(graph=True)), kept across reset()
         self.w_coarse, self.w_color, self.w_logit = self.w[:3]
         self.w_merge = self.w[3] if self.stem else None
+        flags = self.fp16 | ops.MLP_PREPARED_FLAG
+        self.net_c, self.net_col, self.net_log = (Net(w, shp_, flags) for w, (_, shp_) in zip(self.w[:3], nets_w))
+        self.net_m = Net(self.w_merge, self.shp_m, flags) if self.stem else None
         self.lam = (C.c_float * 8)(t.lambda_p, t.lambda_d, t.lambda_l, 0.0, 0.0, 0.0, 0.0, 1.0)
         self.camv = (C.c_double * 4)(float(t.fx), float(t.fy), float(t.cx), float(t.cy))
         self.b6 = ops._bound6(t.bound)
@@ -977,33 +776,17 @@ class TrackStep:
                                     ptr(self.pts), st), "dns_raygen_sample")
         check(lib.dns_track_mask(ptr(self.gt_depth), ptr(self.inside), N, 0.01, ptr(self.valid), st), "dns_track_mask")   # :171-172
         meta = C.byref(self.meta.c)
-        check(lib.dns_encode_fwd(ptr(self.pts), self.b6, P, self.n_bins, ptr(self.p_table), meta, ptr(self.x3), ptr(self.buf), ld,
-                                 _V(self.buf.data_ptr() + 4 * pe), ld, ptr(self.dydx), st), "dns_encode_fwd")
-        fp16 = self.fp16 | self.PREP
-
-        def fwd(x2, n_in1, params, shape, y):
-            n_in, n_out, nn, nl = shape
-            check(lib.dns_mlp_fwd(ptr(self.buf), ld, ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(params), n_in, n_out,
-                                  nn, nl, ptr(y), y.stride(0), P, None, None, 0, None, fp16, st), "dns_mlp_fwd")
-
-        fwd(None, 0, self.w_coarse, self.shp_c, self.lat)                  # coarse-only render (slams/tracking.py:196-200)
+        rows = self.rows
+        rows.encode(self.pts, self.b6, self.n_bins, self.p_table, meta, self.x3, self.dydx, st)
+        rows.fwd(self.net_c, self.lat, st)                                 # coarse-only render (slams/tracking.py:196-200)
         if self.stem:
-            n_in_m, n_out_m, nn_m, nl_m = self.shp_m
-            check(lib.dns_feature_gather_frames(ptr(self.pts), ptr(self.w2c), ptr(self.origin), self.K9, ptr(self.feat_maps), 1, self.R,
-                                                P, self.Cs, self.fh, self.fw, H, W, _V(self.mbuf.data_ptr() + 4 * self.pe_m), n_in_m,
-                                                ptr(self.rel), st), "dns_feature_gather_frames")
-            check(lib.dns_encode_fwd(ptr(self.rel), self.b6m, self.Mr, self.n_bins_m, None, None, ptr(self.xm), ptr(self.mbuf), n_in_m,
-                                     None, 0, None, st), "dns_encode_fwd")
-            check(lib.dns_mlp_fwd(ptr(self.mbuf), n_in_m, None, 0, 0, ptr(self.w_merge), n_in_m, n_out_m, nn_m, nl_m, ptr(self.mlat),
-                                  n_out_m, self.Mr, None, None, 0, None, fp16, st), "dns_mlp_fwd")
-            check(lib.dns_feature_block_split(ptr(self.lat), self.hid + 1, self.hid, ptr(self.mlat), self.hid, self.R, P, ptr(self.z),
-                                              ptr(self.gt_depth), N, S, ptr(self.feat), self.n_feat, None, 0, None, 0, ptr(self.raw), st),
-                  "dns_feature_block_split")
+            s2 = self.stem2d
+            s2.forward(self.pts, self.w2c, self.origin, self.feat_maps, H, W, self.net_m, st)
+            rows.feature_block(self.lat, self.hid, s2.mlat, (self.R, P), self.z, self.gt_depth, N, S, self.raw, st)
         else:
-            check(lib.dns_feature_block(ptr(self.lat), self.hid + 1, self.hid, ptr(self.features), self.n_feat - self.hid, ptr(self.z),
-                                        ptr(self.gt_depth), N, S, ptr(self.feat), self.n_feat, ptr(self.raw), st), "dns_feature_block")
-        fwd(self.feat, pe, self.w_color, self.shp_col, self.raw)
-        fwd(self.feat, pe, self.w_logit, self.shp_log, self.logit)
+            rows.feature_block(self.lat, self.hid, self.features, None, self.z, self.gt_depth, N, S, self.raw, st)
+        rows.fwd(self.net_col, self.raw, st, True)
+        rows.fwd(self.net_log, self.logit, st, True)
         check(lib.dns_rgb_sigmoid(ptr(self.raw), P, st), "dns_rgb_sigmoid")
         Cn = self.n_class
         check(lib.dns_composite_fwd(ptr(self.raw), ptr(self.z), ptr(self.logit), N, S, Cn, ptr(self.depth), ptr(self.var),
@@ -1023,33 +806,17 @@ class TrackStep:
         ldf = 4 + self.n_feat
         check(lib.dns_raw_bwd(ptr(self.d_raw), ptr(self.raw), P, ptr(self.d_col), _V(self.d_featx.data_ptr() + 12), ldf, 0, st),
               "dns_raw_bwd")
-
-        def bwd(x2, n_in1, dy, params, shape, d_x2, acc):
-            n_in, n_out, nn, nl = shape
-            check(lib.dns_mlp_bwd(ptr(self.buf), ld, ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(dy), dy.stride(0),
-                                  ptr(params), n_in, n_out, nn, nl, ptr(self.d_buf), ld, ptr(d_x2),
-                                  0 if d_x2 is None else d_x2.stride(0), None, None, P, None, None, 0, None, acc | fp16, st),
-                  "dns_mlp_bwd")
-
-        d_feat = self.d_featx[:, 4:]
-        bwd(self.feat, pe, self.d_col, self.w_color, self.shp_col, d_feat, 1)        # d_buf (zeroed) += ; feature block =
-        bwd(self.feat, pe, self.d_logit, self.w_logit, self.shp_log, d_feat, 3)
+        d_buf, d_feat = self.d_buf, self.d_feat                             # the scene is frozen: no weight gradients
+        rows.bwd(self.net_col, self.d_col, d_buf, d_feat, None, None, 1, st)  # d_buf (zeroed) += ; feature block =
+        rows.bwd(self.net_log, self.d_logit, d_buf, d_feat, None, None, 3, st)
         if self.stem:
-            n_in_m, n_out_m, nn_m, nl_m = self.shp_m
-            pe_m = self.pe_m
-            check(lib.dns_merge_dy(_V(self.d_featx.data_ptr() + 4 * (4 + self.hid)), ldf, n_out_m, self.R, P, ptr(self.z),
-                                   ptr(self.gt_depth), N, S, ptr(self.mdy), st), "dns_merge_dy")
-            check(lib.dns_mlp_bwd(ptr(self.mbuf), n_in_m, _V(self.mbuf.data_ptr() + 4 * pe_m), n_in_m, pe_m, ptr(self.mdy), n_out_m,
-                                  ptr(self.w_merge), n_in_m, n_out_m, nn_m, nl_m, ptr(self.d_mpe), pe_m, None, 0, None, None, self.Mr,
-                                  None, None, 0, None, ops.MLP_DX_FIRST_FLAG | fp16, st), "dns_mlp_bwd")
-            check(lib.dns_encode_bwd(ptr(self.xm), self.b6m, self.Mr, self.n_bins_m, None, None, ptr(self.d_mpe), pe_m, None, 0, None,
-                                     ptr(self.d_rel), None, None, 0, 0, st), "dns_encode_bwd")
-        bwd(None, 0, self.d_featx[:, 3:3 + self.hid + 1], self.w_coarse, self.shp_c, None, 1)
+            s2.backward(_V(self.d_featx.data_ptr() + 4 * (4 + self.hid)), ldf, self.z, self.gt_depth, N, S, self.net_m, None, st)
+        rows.bwd(self.net_c, self.d_lat, d_buf, None, None, None, 1, st)
         check(lib.dns_encode_bwd(ptr(self.x3), self.b6, P, self.n_bins, ptr(self.p_table), meta, ptr(self.d_buf), ld,
                                  _V(self.d_buf.data_ptr() + 4 * pe), ld, None, ptr(self.d_x3), ptr(self.dydx), None, 0, 0, st),
               "dns_encode_bwd")
         if self.stem:
-            check(lib.dns_add_ref_sum(ptr(self.d_rel), self.R, P, P, ptr(self.d_x3), st), "dns_add_ref_sum")
+            s2.add_ref_sum(P, self.d_x3, st)
         check(lib.dns_raygen_bwd(ptr(pix), ptr(self.Q), self.camv, b, H - b, b, W - b, 1, N, S, ptr(self.z), ptr(self.d_x3), None,
                                  None, ptr(self.ray_ws), ptr(self.g_quat), ptr(self.g_trans), st), "dns_raygen_bwd")
         check(lib.dns_adam_step(self.adam_items, 2, self.betas[0], self.betas[1], self.eps, ptr(self.adam_state), st),
@@ -1097,10 +864,7 @@ class TrackStep:
         for k, v in (("color", cur_frames["gt_color"]), ("depth", cur_frames["gt_depth"]), ("label", cur_frames["gt_label"])):
             self.prep[k].copy_(v.to(dev).float()[None])
         if self.stem:
-            self.feat_maps.copy_(features.detach().to(dev).float()[0].permute(0, 2, 3, 1))
-            w2c = refer_frames["est_w2c"].clone().detach().to(dev).float()
-            self.w2c.copy_(w2c.reshape(self.R, 16))
-            self.origin.copy_(torch.inverse(w2c)[:, :3, 3])
+            self._set_views(features, refer_frames)
         elif self.features is not None:
             self.features.copy_(features.to(dev).float())
         self.Q.copy_(get_quad_from_c2w(est_c2w).detach().to(dev).float().reshape(1, 4))
@@ -1112,6 +876,12 @@ class TrackStep:
         self.best_cam.copy_(torch.cat((self.Q.reshape(-1), self.T.reshape(-1))))
         self._prepare_weights()
         self.steps = 0
+
+    def _set_views(self, features, refer_frames):
+        w2c = refer_frames["est_w2c"].clone().detach().to(self.dev).float()             # slams/tracking.py:162
+        self.feat_maps.copy_(features.detach().to(self.dev).float()[0].permute(0, 2, 3, 1))
+        self.w2c.copy_(w2c.reshape(self.R, 16))
+        self.origin.copy_(torch.inverse(w2c)[:, :3, 3])                                  # utils/common.py:672-674
 
     def _prepare_weights(self):
         st = _V(torch.cuda.current_stream().cuda_stream)
@@ -1180,9 +950,8 @@ class TrackStep:
         n_ws = int(ops.lib._raw.dns_track_fused_ws_floats(C.byref(a)))
         if n_ws == 0:
             return None
-        keep["ws"] = torch.empty(n_ws + 64, device=dev)
-        off = (-keep["ws"].data_ptr() // 4) % 64                       # 256-byte aligned start
-        a.ws = keep["ws"].data_ptr() + 4 * off
+        keep["ws"] = aligned_floats(n_ws, 64, dev)                     # 256-byte aligned start
+        a.ws = keep["ws"].data_ptr()
         self._fb = {"n_iters": key, "args": a, "keep": keep, "graph": None}
         return self._fb
 
@@ -1207,7 +976,6 @@ class TrackStep:
             for k, v in zip(("pix", "t_surf", "t_zero"), draws):
                 keep[k].copy_(v.to(self.dev))
         keep["iter"].zero_()
-        self._prepare_weights_if_stale()
         check(lib.dns_track_fused_begin(ptr(keep["pix"]), N, n_iters, ptr(self.prep["depth"]), W, b, b, W - b, ptr(keep["t_surf"]), self.ns,
                                         ptr(keep["dmax"]), st), "dns_track_fused_begin")
         if not graph:
@@ -1227,9 +995,6 @@ class TrackStep:
         self.steps += n_iters
         self.fused_out = keep["out"]
         return self.best_cam, self.best_loss[0]
-
-    def _prepare_weights_if_stale(self):
-        pass                                               # (reset() rebuilds the operand images per frame; nothing to do here)
 
     def run(self, n_iters, graph=True):
         """n_iters iterations -> (best camera tensor [7] = (quat | T), best loss).  ``graph``: capture one iteration into a

@@ -271,6 +271,42 @@ MLP_DX_FROM = lambda c: int(c) << 24       # include/dns_hip.h DNS_MLP_DX_FROM(c
 MLP_LIVE_IN = lambda n: int(n) << 16       # include/dns_hip.h DNS_MLP_LIVE_IN(n): input columns [n, n_in) are identically zero
 
 
+# ---- the MLP entry points on fp32 and half rows, each spelled positionally ONCE inside the package (the split-row pair: launch.
+# SplitRows; tests and tools keep direct calls: they exercise the ABI).  Tensors or None in; the pointers, the row strides and the
+# zero stride of an absent tensor are formed here.  ``lib`` is read at call time, so a timer armed after a step was built still
+# brackets every launch (bench.py's per-kernel table).  ``shape`` = (n_in, n_out, n_neurons, n_hidden_layers).
+def launch_mlp_fwd(x, x2, n_in1, w, shape, y, n_slots, row_index, tile_group, stride, h_save, flags, st):
+    check(lib.dns_mlp_fwd(ptr(x), x.stride(0), ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(w), *shape, ptr(y), y.stride(0),
+                          n_slots, ptr(row_index), ptr(tile_group), stride, ptr(h_save), flags, st), "dns_mlp_fwd")
+
+
+def launch_mlp_bwd(x, x2, n_in1, dy, w, shape, d_x, d_x2, d_params, ws, n_slots, row_index, tile_group, stride, h_saved, flags, st):
+    check(lib.dns_mlp_bwd(ptr(x), x.stride(0), ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(dy), dy.stride(0), ptr(w),
+                          *shape, ptr(d_x), 0 if d_x is None else d_x.stride(0), ptr(d_x2), 0 if d_x2 is None else d_x2.stride(0),
+                          ptr(d_params), ptr(ws), n_slots, ptr(row_index), ptr(tile_group), stride, ptr(h_saved), flags, st),
+          "dns_mlp_bwd")
+
+
+def launch_mlp_dwin(x, x2, n_in1, shape, d_params, ws, n_slots, row_index, tile_group, stride, flags, st):
+    check(lib.dns_mlp_dwin(ptr(x), x.stride(0), ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, shape[0], shape[2], shape[3],
+                           ptr(d_params), ptr(ws), n_slots, ptr(row_index), ptr(tile_group), stride, flags, st), "dns_mlp_dwin")
+
+
+def launch_mlp_fwd_half(x, x2, n_in1, w, shape, y, n_slots, row_index, tile_group, stride, flags, st, ldx2=0):
+    """``ldx2``: what an ABSENT x2 passes as its row stride (MapStep's single-segment launches have always passed their feature
+    block's width there; the kernels read it with x2 alone)."""
+    check(lib.dns_mlp_fwd_half(ptr(x), x.stride(0), ptr(x2), ldx2 if x2 is None else x2.stride(0), n_in1, ptr(w), *shape, ptr(y),
+                               y.stride(0), n_slots, ptr(row_index), ptr(tile_group), stride, flags, st), "dns_mlp_fwd_half")
+
+
+def launch_mlp_bwd_half(x, x2, n_in1, dy, w, shape, d_x, d_x2, d_params, n_slots, row_index, tile_group, stride, flags, loss_scale,
+                        st, ldx2=0):
+    check(lib.dns_mlp_bwd_half(ptr(x), x.stride(0), ptr(x2), ldx2 if x2 is None else x2.stride(0), n_in1, ptr(dy), dy.stride(0),
+                               ptr(w), *shape, ptr(d_x), 0 if d_x is None else d_x.stride(0), ptr(d_x2),
+                               0 if d_x2 is None else d_x2.stride(0), ptr(d_params), n_slots, ptr(row_index), ptr(tile_group),
+                               stride, flags, loss_scale, st), "dns_mlp_bwd_half")
+
+
 class _MlpFn(torch.autograd.Function):
     """y = MLP(x; params).  ``params`` is [G, count] (G weight sets, G=1 for a plain network)."""
 
@@ -292,8 +328,7 @@ class _MlpFn(torch.autograd.Function):
         # keep the hidden activations when a backward will follow: it then skips the forward recompute
         keep = MLP_SAVE_HIDDEN and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         h_save = torch.empty(nl * n_slots * nn, device=x.device, dtype=torch.float32) if keep else None
-        check(lib.dns_mlp_fwd(ptr(x), x.stride(0), None, 0, 0, ptr(params), n_in, n_out, nn, nl, ptr(y), n_out, n_slots,
-                              ptr(row_index), ptr(tile_group), stride, ptr(h_save), fp16, stream_ptr()), "dns_mlp_fwd")
+        launch_mlp_fwd(x, None, 0, params, shape[:4], y, n_slots, row_index, tile_group, stride, h_save, fp16, stream_ptr())
         ctx.save_for_backward(x, params, row_index, tile_group, h_save)
         ctx.shape, ctx.n_slots, ctx.stride, ctx.fp16 = shape[:4], n_slots, stride, fp16
         return y
@@ -311,9 +346,8 @@ class _MlpFn(torch.autograd.Function):
             d_x = torch.zeros(P, n_in, device=x.device, dtype=torch.float32) if need_x else None
         d_p = torch.zeros_like(params) if need_p else None
         ws = torch.empty(int(lib.dns_mlp_bwd_ws_floats(ctx.n_slots, nn, nl)), device=x.device, dtype=torch.float32)
-        check(lib.dns_mlp_bwd(ptr(x), x.stride(0), None, 0, 0, ptr(dy), n_out, ptr(params), n_in, n_out, nn, nl,
-                              ptr(d_x), n_in, None, 0, ptr(d_p), ptr(ws), ctx.n_slots, ptr(row_index), ptr(tile_group),
-                              ctx.stride, ptr(h_save), ctx.fp16, stream_ptr()), "dns_mlp_bwd")
+        launch_mlp_bwd(x, None, 0, dy, params, ctx.shape, d_x, None, d_p, ws, ctx.n_slots, row_index, tile_group, ctx.stride, h_save,
+                       ctx.fp16, stream_ptr())
         return d_x, d_p, None, None, None, None
 
 
@@ -332,8 +366,7 @@ class _MlpCatFn(torch.autograd.Function):
         P, n1 = x1.shape
         y = torch.empty(P, n_out, device=x1.device, dtype=torch.float32)
         h_save = torch.empty(nl * P * nn, device=x1.device, dtype=torch.float32) if MLP_SAVE_HIDDEN else None
-        check(lib.dns_mlp_fwd(ptr(x1), x1.stride(0), ptr(x2), x2.stride(0), n1, ptr(params), n_in, n_out, nn, nl, ptr(y),
-                              n_out, P, None, None, 0, ptr(h_save), fp16, stream_ptr()), "dns_mlp_fwd")
+        launch_mlp_fwd(x1, x2, n1, params, shape[:4], y, P, None, None, 0, h_save, fp16, stream_ptr())
         ctx.save_for_backward(x1, x2, params, h_save)
         ctx.shape, ctx.fp16 = shape[:4], fp16
         return y
@@ -349,9 +382,7 @@ class _MlpCatFn(torch.autograd.Function):
         d2 = torch.empty(P, n_in - n1, device=x1.device, dtype=torch.float32) if need_x else None
         d_p = torch.zeros_like(params) if ctx.needs_input_grad[2] else None
         ws = torch.empty(int(lib.dns_mlp_bwd_ws_floats(P, nn, nl)), device=x1.device, dtype=torch.float32)
-        check(lib.dns_mlp_bwd(ptr(x1), x1.stride(0), ptr(x2), x2.stride(0), n1, ptr(dy), n_out, ptr(params), n_in, n_out, nn, nl,
-                              ptr(d1), n1, ptr(d2), n_in - n1, ptr(d_p), ptr(ws), P, None, None, 0, ptr(h_save), ctx.fp16,
-                              stream_ptr()), "dns_mlp_bwd")
+        launch_mlp_bwd(x1, x2, n1, dy, params, ctx.shape, d1, d2, d_p, ws, P, None, None, 0, h_save, ctx.fp16, stream_ptr())
         return (d1 if ctx.needs_input_grad[0] else None), (d2 if ctx.needs_input_grad[1] else None), d_p, None
 
 
@@ -408,9 +439,8 @@ def mlp_fwd_half(x, params, n_in, n_out, n_neurons, n_hidden_layers, x2=None, ro
     n_slots = rows if n_slots is None else n_slots
     y = out if out is not None else torch.zeros(rows, n_out, device=x.device, dtype=torch.float32)
     n_in1 = x.shape[1] if x2 is not None else 0
-    check(lib.dns_mlp_fwd_half(ptr(x), x.stride(0), ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(params), n_in, n_out,
-                               n_neurons, n_hidden_layers, ptr(y), y.stride(0), n_slots, ptr(row_index), ptr(tile_group), param_stride,
-                               MLP_LIVE_IN(live_in) if live_in else 0, stream_ptr()), "dns_mlp_fwd_half")
+    launch_mlp_fwd_half(x, x2, n_in1, params, (n_in, n_out, n_neurons, n_hidden_layers), y, n_slots, row_index, tile_group, param_stride,
+                        MLP_LIVE_IN(live_in) if live_in else 0, stream_ptr())
     return y
 
 
@@ -425,10 +455,8 @@ def mlp_bwd_half(x, dy, params, n_in, n_out, n_neurons, n_hidden_layers, x2=None
         raise ValueError("mlp_bwd_half: x / x2 must be 2-D float16 CUDA tensors with unit column stride")
     n_slots = x.shape[0] if n_slots is None else n_slots
     n_in1 = x.shape[1] if x2 is not None else 0
-    check(lib.dns_mlp_bwd_half(ptr(x), x.stride(0), ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(dy), dy.stride(0),
-                               ptr(params), n_in, n_out, n_neurons, n_hidden_layers, ptr(d_x), 0 if d_x is None else d_x.stride(0),
-                               ptr(d_x2), 0 if d_x2 is None else d_x2.stride(0), ptr(d_params), n_slots, ptr(row_index),
-                               ptr(tile_group), param_stride, int(accumulate), float(loss_scale), stream_ptr()), "dns_mlp_bwd_half")
+    launch_mlp_bwd_half(x, x2, n_in1, dy, params, (n_in, n_out, n_neurons, n_hidden_layers), d_x, d_x2, d_params, n_slots, row_index,
+                        tile_group, param_stride, int(accumulate), float(loss_scale), stream_ptr())
 
 
 def group_slots(slot_of_point: torch.Tensor, n_groups: int, min_count: int = 2):
@@ -486,11 +514,8 @@ class _RenderNetsFn(torch.autograd.Function):
         st = stream_ptr()
 
         def run(x, x2, n_in1, params, shape, y, ri, tg, n_slots, stride, live=0):
-            n_in, n_out, nn, nl = shape
-            h = torch.empty(nl * n_slots * nn, device=dev, dtype=torch.float32) if keep else None
-            check(lib.dns_mlp_fwd(ptr(x), x.stride(0), ptr(x2), 0 if x2 is None else x2.stride(0), n_in1, ptr(params),
-                                  n_in, n_out, nn, nl, ptr(y), y.stride(0), n_slots, ptr(ri), ptr(tg), stride, ptr(h), fp16 | live, st),
-                  "dns_mlp_fwd")
+            h = torch.empty(shape[3] * n_slots * shape[2], device=dev, dtype=torch.float32) if keep else None
+            launch_mlp_fwd(x, x2, n_in1, params, shape, y, n_slots, ri, tg, stride, h, fp16 | live, st)
             return h
 
         # (need_coarse = False: the forward-only frame render, slams/mapping.py:638-694 -- the coarse latents feed the latent
@@ -554,13 +579,9 @@ class _RenderNetsFn(torch.autograd.Function):
                for p, o, z, n in zip((coarse_p, fine_pool, color_p, logit_p), offs, sizes, need)}
 
         def run(x, x2, n_in1, dy, params, shape, d_x, d_x2, need_p, ri_, tg_, n_slots, stride, h, acc):
-            n_in, n_out, nn, nl = shape
             d_p = dps[id(params)] if need_p else None
-            ws = torch.empty(int(lib.dns_mlp_bwd_ws_floats(n_slots, nn, nl)), device=dev, dtype=torch.float32)
-            check(lib.dns_mlp_bwd(ptr(x), x.stride(0), ptr(x2), 0 if x2 is None else x2.stride(0), n_in1,
-                                  ptr(dy), dy.stride(0), ptr(params), n_in, n_out, nn, nl,
-                                  ptr(d_x), d_x.stride(0), ptr(d_x2), 0 if d_x2 is None else d_x2.stride(0),
-                                  ptr(d_p), ptr(ws), n_slots, ptr(ri_), ptr(tg_), stride, ptr(h), acc | fp16, st), "dns_mlp_bwd")
+            ws = torch.empty(int(lib.dns_mlp_bwd_ws_floats(n_slots, shape[2], shape[3])), device=dev, dtype=torch.float32)
+            launch_mlp_bwd(x, x2, n_in1, dy, params, shape, d_x, d_x2, d_p, ws, n_slots, ri_, tg_, stride, h, acc | fp16, st)
             return d_p
 
         def grad(d, like_cols):

@@ -274,7 +274,7 @@ def test_map_step_on_half_rows_tracks_the_fp16_operand_and_fp32_steps(monkeypatc
     from dns_slam_amd.fused_step import MapStep
     from util import randomise_
     res = {}
-    for mode in ("fp32", "operand", "half"):
+    for mode in ("fp32", "operand", "operand_split", "half"):
         monkeypatch.setenv("DNS_HALF_ROWS", "1" if mode == "half" else "0")
         cam = synthetic.camera(H=60, W=80, fx=60.0, fy=60.0)
         bound, cam, frames = synthetic.make_scene(4, cam=cam, seed=0)
@@ -289,8 +289,8 @@ def test_map_step_on_half_rows_tracks_the_fp16_operand_and_fp32_steps(monkeypatc
         randomise_([mapper.fine_decoders.pool], 12)
         mapper.static_shapes, mapper.is_BA, mapper.overlap_smooth, mapper.prefetch_draws = True, True, True, True
         _, ql, Tl = mapper.set_optimizer(frames, fused=True)
-        ms = MapStep(mapper, frames, ql, Tl)
-        assert ms.half == (mode == "half") and bool(ms.fp16) == (mode != "fp32")
+        ms = MapStep(mapper, frames, ql, Tl, split_rows=True if mode == "operand_split" else None)
+        assert ms.half == (mode == "half") and bool(ms.fp16) == (mode != "fp32") and (ms.sr or mode != "operand_split")
         torch.manual_seed(5)
         torch.cuda.manual_seed(5)
         ms.step()
@@ -309,5 +309,13 @@ def test_map_step_on_half_rows_tracks_the_fp16_operand_and_fp32_steps(monkeypatc
     for n in h["g"]:
         assert rel(h["g"][n], o["g"][n]) <= 2e-2, (n, rel(h["g"][n], o["g"][n]))
         assert rel(h["g"][n], f["g"][n]) <= 1e-1, (n, rel(h["g"][n], f["g"][n]))
+    # the fp16-operand step on hi-only split rows (split_rows=True): held to the fp16-operand step by the same bounds
+    s = res["operand_split"][0]
+    assert abs(s["loss"] - o["loss"]) <= 2e-3 * abs(o["loss"])
+    for k in s["terms"]:
+        assert abs(s["terms"][k] - o["terms"][k]) <= 5e-3 * max(abs(o["terms"][k]), 1e-3), k
+    for n in s["g"]:
+        assert rel(s["g"][n], o["g"][n]) <= 2e-2, (n, rel(s["g"][n], o["g"][n]))
+    assert res["operand_split"][1] < 0.9 * s["loss"], "the fp16-operand step on split rows does not train"
     assert res["half"][1] < 0.9 * h["loss"], "the half-rows step does not train"
     assert abs(res["half"][1] - res["fp32"][1]) <= 0.1 * abs(res["fp32"][1])
