@@ -9,8 +9,10 @@
 // Bound: memory system (random 8-B gathers, 1024 B per point), not MFMA.
 //
 // Arithmetic contract shared with oracle/tcnn_ref.py: pos = x*scale + 0.5 is two IEEE roundings
-// (__fmul_rn/__fadd_rn, never contracted), the cell is (uint32)(int)floorf(pos); hash primes
-// {1, 2654435761, 805459861}; index % level size.  Those make the table rows bit-exact.
+// (never contracted), the cell is (uint32)(int)floorf(pos); hash primes
+// {1, 2654435761, 805459861}; index % level size.  Those make the table rows bit-exact.  The arithmetic
+// itself -- cell, weights, level gather, OneBlob -- lives in dev_encode.hpp, one spelling for these kernels,
+// the table scatter and the fused tracker; this file owns the tiles, the phases and the launches.
 #include <type_traits>
 #include "common.hpp"
 #include "split_rows.hpp"
@@ -18,6 +20,20 @@
 #include "scatter_plan.hpp"
 
 namespace dns {
+
+// The (row, column group) pairs of a rows x nq tile, dealt to the workgroup's threads in row-major order: fn(r, c).  (row, column)
+// advance incrementally: an integer division per element was a visible cost.
+template <typename F>
+__device__ __forceinline__ void tile_walk(uint32_t rows, uint32_t nq, F fn) {
+  const uint32_t dr = blockDim.x / nq, dc = blockDim.x - dr * nq;
+  uint32_t r = threadIdx.x / nq, c = threadIdx.x - r * nq;
+  for (uint32_t i = threadIdx.x; i < rows * nq; i += blockDim.x) {
+    fn(r, c);
+    r += dr;
+    c += dc;
+    if (c >= nq) { c -= nq; ++r; }
+  }
+}
 
 // One lane = one point.  TILED = the [P, 3*n_bins + 2*L] output rows are contiguous (OneBlob | grid in one buffer):
 // the lane's channels go to an LDS tile (row stride +1 float: conflict-free) and the workgroup's tile leaves as one
@@ -63,72 +79,33 @@ __global__ __launch_bounds__(128) void encode_fwd_kernel(const float* __restrict
     const uint32_t p0 = blockIdx.x * blockDim.x;
     const uint32_t rows = min(blockDim.x, P - p0);
     float* out = out_base + (size_t)p0 * ld;
-    // (row, column) advance incrementally (an integer division per element was a visible cost); 16-byte global accesses
-    // where the rows allow it (the LDS tile's odd row stride keeps its side at dwords)
+    // 16-byte global accesses where the rows allow it (the LDS tile's odd row stride keeps its side at dwords)
     if constexpr (HALF) {                              // nc, ld multiples of 8, out_base 16-byte aligned (host-checked)
       _Float16* outh = reinterpret_cast<_Float16*>(out_base) + (size_t)p0 * ld;
-      const uint32_t nq = nc >> 3, dr = blockDim.x / nq, dc = blockDim.x - dr * nq;
-      uint32_t r = threadIdx.x / nq, c = threadIdx.x - r * nq;
-      for (uint32_t i = threadIdx.x; i < rows * nq; i += blockDim.x) {
+      tile_walk(rows, nc >> 3, [&](uint32_t r, uint32_t c) {
         const float* t = tile + r * ldt + 8 * c;
         typedef _Float16 half8v __attribute__((ext_vector_type(8)));
         half8v h;
 #pragma unroll
         for (int k = 0; k < 8; ++k) h[k] = (_Float16)t[k];
         *reinterpret_cast<half8v*>(outh + (size_t)r * ld + 8 * c) = h;
-        r += dr;
-        c += dc;
-        if (c >= nq) { c -= nq; ++r; }
-      }
+      });
     } else if (((nc | ld) & 3u) == 0 && ((((uintptr_t)out_base) & 15u) == 0)) {
-      const uint32_t nq = nc >> 2, dr = blockDim.x / nq, dc = blockDim.x - dr * nq;
-      uint32_t r = threadIdx.x / nq, c = threadIdx.x - r * nq;
-      for (uint32_t i = threadIdx.x; i < rows * nq; i += blockDim.x) {
+      tile_walk(rows, nc >> 2, [&](uint32_t r, uint32_t c) {
         const float* t = tile + r * ldt + 4 * c;
         *reinterpret_cast<float4*>(out + (size_t)r * ld + 4 * c) = make_float4(t[0], t[1], t[2], t[3]);
-        r += dr;
-        c += dc;
-        if (c >= nq) { c -= nq; ++r; }
-      }
+      });
     } else {
-      const uint32_t dr = blockDim.x / nc, dc = blockDim.x - dr * nc;
-      uint32_t r = threadIdx.x / nc, c = threadIdx.x - r * nc;
-      for (uint32_t i = threadIdx.x; i < rows * nc; i += blockDim.x) {
-        out[(size_t)r * ld + c] = tile[r * ldt + c];
-        r += dr;
-        c += dc;
-        if (c >= nc) { c -= nc; ++r; }
-      }
+      tile_walk(rows, nc, [&](uint32_t r, uint32_t c) { out[(size_t)r * ld + c] = tile[r * ldt + c]; });
     }
     __syncthreads();
   };
   if (pe_out) {
-    const float n = (float)n_bins;
     float* row = TILED ? trow : pe_out + (size_t)p * ld_pe;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const uint32_t c0 = (TILED && pe_ph == 3u) ? 0u : a * n_bins;      // the axis' first tile / row column
-      if (live) {
-        const float xa = x[a];
-        if (n_bins >= 8u && fabsf(xa) < 4.0f) {            // windows of different images cannot overlap
-          for (uint32_t b = 0; b < n_bins; ++b) row[c0 + b] = 0.f;
-          oneblob_windows<false>(n_bins, n, xa, [&](uint32_t j, float v) { row[c0 + j] = v; });
-        } else {
-          float first = 0.f, left = 0.f;
-          for (uint32_t b = 0; b <= n_bins; ++b) {
-            float g;
-            if (b < n_bins) {
-              const float d = (float)b / n - xa;
-              g = quartic_cdf(d, n) + quartic_cdf(d - 1.0f, n) + quartic_cdf(d + 1.0f, n);
-              if (b == 0) first = g;
-            } else {
-              g = first + 1.0f;  // right edge of the last bin wraps (tcnn kernel_one_blob)
-            }
-            if (b > 0) row[c0 + b - 1] = g - left;
-            left = g;
-          }
-        }
-      }
+      if (live) oneblob_axis_fwd(x[a], n_bins, row + c0);
       if (TILED && pe_ph == 3u) flush(col_ptr(pe_out, a * n_bins), ld_pe, n_bins);
     }
     if (TILED && pe_ph != 3u) flush(pe_out, ld_pe, pe_dim);
@@ -138,49 +115,7 @@ __global__ __launch_bounds__(128) void encode_fwd_kernel(const float* __restrict
     if (live) {
       float* row = TILED ? trow - 2u * lpp * ph : grid_out + (size_t)p * ld_grid;     // (TILED: level l's pair at tile column 2 (l - lpp ph))
 #pragma unroll 4
-      for (uint32_t l = lpp * ph; l < lpp * (ph + 1u); ++l) {
-        const float s = lv.scale[l];
-        const uint32_t res = lv.resolution[l], size = lv.size[l], hashed = lv.hashed[l];
-        const float2* __restrict__ t = table + lv.offset[l];
-        float f[3];
-        uint32_t g[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const float pos = __fadd_rn(__fmul_rn(x[a], s), 0.5f);
-          const float fl = floorf(pos);
-          g[a] = (uint32_t)(int)fl;
-          f[a] = pos - fl;
-        }
-        float2 v[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-          v[c] = t[grid_row(g[0] + (c & 1), g[1] + ((c >> 1) & 1), g[2] + ((c >> 2) & 1), res, size, hashed)];
-        float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const float w = ((c & 1) ? f[0] : 1.0f - f[0]) * ((c & 2) ? f[1] : 1.0f - f[1]) * ((c & 4) ? f[2] : 1.0f - f[2]);
-          a0 += w * v[c].x;
-          a1 += w * v[c].y;
-        }
-        row[2 * l] = a0;
-        row[2 * l + 1] = a1;
-        if (dydx) {
-          // d(feature) / d(normalised coordinate), both features, per axis -- what tcnn's kernel_grid keeps as dy_dx when the
-          // input needs a gradient (the poses do, through pts): the backward then needs no second gather of the 8 corners.
-          // Layout [level][axis][point] float2: a wave's 64 points are 512 contiguous bytes per store.
-          const float wx0 = 1.0f - f[0], wx1 = f[0], wy0 = 1.0f - f[1], wy1 = f[1], wz0 = 1.0f - f[2], wz1 = f[2];
-          float2 jx, jy, jz;
-          jx.x = s * (wy0 * wz0 * (v[1].x - v[0].x) + wy1 * wz0 * (v[3].x - v[2].x) + wy0 * wz1 * (v[5].x - v[4].x) + wy1 * wz1 * (v[7].x - v[6].x));
-          jx.y = s * (wy0 * wz0 * (v[1].y - v[0].y) + wy1 * wz0 * (v[3].y - v[2].y) + wy0 * wz1 * (v[5].y - v[4].y) + wy1 * wz1 * (v[7].y - v[6].y));
-          jy.x = s * (wx0 * wz0 * (v[2].x - v[0].x) + wx1 * wz0 * (v[3].x - v[1].x) + wx0 * wz1 * (v[6].x - v[4].x) + wx1 * wz1 * (v[7].x - v[5].x));
-          jy.y = s * (wx0 * wz0 * (v[2].y - v[0].y) + wx1 * wz0 * (v[3].y - v[1].y) + wx0 * wz1 * (v[6].y - v[4].y) + wx1 * wz1 * (v[7].y - v[5].y));
-          jz.x = s * (wx0 * wy0 * (v[4].x - v[0].x) + wx1 * wy0 * (v[5].x - v[1].x) + wx0 * wy1 * (v[6].x - v[2].x) + wx1 * wy1 * (v[7].x - v[3].x));
-          jz.y = s * (wx0 * wy0 * (v[4].y - v[0].y) + wx1 * wy0 * (v[5].y - v[1].y) + wx0 * wy1 * (v[6].y - v[2].y) + wx1 * wy1 * (v[7].y - v[3].y));
-          dydx[((size_t)l * 3 + 0) * P + p] = jx;
-          dydx[((size_t)l * 3 + 1) * P + p] = jy;
-          dydx[((size_t)l * 3 + 2) * P + p] = jz;
-        }
-      }
+      for (uint32_t l = lpp * ph; l < lpp * (ph + 1u); ++l) grid_level(table, lv, l, x, row, dydx, P, p);
     }
     if (TILED) flush(col_ptr(grid_out, 2u * lpp * ph), ld_grid, 2u * lpp);
     }
@@ -221,50 +156,22 @@ __global__ __launch_bounds__(128) void encode_fwd_split_kernel(const float* __re
     const uint32_t p0 = blockIdx.x * blockDim.x;
     const uint32_t rows = min(blockDim.x, P - p0);
     uint32_t* out = out_base + (size_t)p0 * ld + c0;
-    const uint32_t nq = nc >> 2, dr = blockDim.x / nq, dc = blockDim.x - dr * nq;
-    uint32_t r = threadIdx.x / nq, c = threadIdx.x - r * nq;
-    for (uint32_t i = threadIdx.x; i < rows * nq; i += blockDim.x) {
+    tile_walk(rows, nc >> 2, [&](uint32_t r, uint32_t c) {
       const uint32_t* t = reinterpret_cast<const uint32_t*>(tile) + r * ldt + tc0 + 4 * c;
       *reinterpret_cast<uint4*>(out + (size_t)r * ld + 4 * c) = make_uint4(t[0], t[1], t[2], t[3]);
-      r += dr;
-      c += dc;
-      if (c >= nq) { c -= nq; ++r; }
-    }
+    });
     __syncthreads();
-  };
-  auto oneblob_row = [&]() -> float {                     // the lane's pe_dim OneBlob values -> its tile row; their maximum
-    const float n = (float)n_bins;
-    float m = 0.f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float xa = x[a];
-      if (n_bins >= 8u && fabsf(xa) < 4.0f) {
-        for (uint32_t b = 0; b < n_bins; ++b) trow[a * n_bins + b] = 0.f;
-        oneblob_windows<false>(n_bins, n, xa, [&](uint32_t j, float v) { trow[a * n_bins + j] = v; m = fmaxf(m, fabsf(v)); });
-        continue;
-      }
-      float first = 0.f, left = 0.f;
-      for (uint32_t b = 0; b <= n_bins; ++b) {
-        float g;
-        if (b < n_bins) {
-          const float d = (float)b / n - xa;
-          g = quartic_cdf(d, n) + quartic_cdf(d - 1.0f, n) + quartic_cdf(d + 1.0f, n);
-          if (b == 0) first = g;
-        } else {
-          g = first + 1.0f;
-        }
-        if (b > 0) { trow[a * n_bins + b - 1] = g - left; m = fmaxf(m, fabsf(g - left)); }
-        left = g;
-      }
-    }
-    return m;
   };
   // ---- A
   float rmax = 0.f;
   bool bad = false;                                       // fmaxf drops a NaN: a non-finite value must reach the exponent rule
   if (live) {
-    rmax = oneblob_row();
-    for (uint32_t c = 0; c < pe_dim; ++c) bad = bad || !(fabsf(trow[c]) < INFINITY);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) oneblob_axis_fwd(x[a], n_bins, trow + a * n_bins);
+    for (uint32_t c = 0; c < pe_dim; ++c) {
+      rmax = fmaxf(rmax, fabsf(trow[c]));
+      bad = bad || !(fabsf(trow[c]) < INFINITY);
+    }
   }
   if (f32_out) flush(reinterpret_cast<uint32_t*>(f32_out), ld32, 0, pe_dim, 0);
   else __syncthreads();
@@ -273,46 +180,9 @@ __global__ __launch_bounds__(128) void encode_fwd_split_kernel(const float* __re
   if (live) {
 #pragma unroll 4
     for (uint32_t l = 0; l < lv.n_levels; ++l) {
-      const float s = lv.scale[l];
-      const uint32_t res = lv.resolution[l], size = lv.size[l], hashed = lv.hashed[l];
-      const float2* __restrict__ t = table + lv.offset[l];
-      float f[3];
-      uint32_t g[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float pos = __fadd_rn(__fmul_rn(x[a], s), 0.5f);
-        const float fl = floorf(pos);
-        g[a] = (uint32_t)(int)fl;
-        f[a] = pos - fl;
-      }
-      float2 v[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-        v[c] = t[grid_row(g[0] + (c & 1), g[1] + ((c >> 1) & 1), g[2] + ((c >> 2) & 1), res, size, hashed)];
-      float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const float w = ((c & 1) ? f[0] : 1.0f - f[0]) * ((c & 2) ? f[1] : 1.0f - f[1]) * ((c & 4) ? f[2] : 1.0f - f[2]);
-        a0 += w * v[c].x;
-        a1 += w * v[c].y;
-      }
-      trow[2 * l] = a0;
-      trow[2 * l + 1] = a1;
-      rmax = fmaxf(rmax, fmaxf(fabsf(a0), fabsf(a1)));
-      bad = bad || !(fabsf(a0) < INFINITY) || !(fabsf(a1) < INFINITY);
-      if (dydx) {
-        const float wx0 = 1.0f - f[0], wx1 = f[0], wy0 = 1.0f - f[1], wy1 = f[1], wz0 = 1.0f - f[2], wz1 = f[2];
-        float2 jx, jy, jz;
-        jx.x = s * (wy0 * wz0 * (v[1].x - v[0].x) + wy1 * wz0 * (v[3].x - v[2].x) + wy0 * wz1 * (v[5].x - v[4].x) + wy1 * wz1 * (v[7].x - v[6].x));
-        jx.y = s * (wy0 * wz0 * (v[1].y - v[0].y) + wy1 * wz0 * (v[3].y - v[2].y) + wy0 * wz1 * (v[5].y - v[4].y) + wy1 * wz1 * (v[7].y - v[6].y));
-        jy.x = s * (wx0 * wz0 * (v[2].x - v[0].x) + wx1 * wz0 * (v[3].x - v[1].x) + wx0 * wz1 * (v[6].x - v[4].x) + wx1 * wz1 * (v[7].x - v[5].x));
-        jy.y = s * (wx0 * wz0 * (v[2].y - v[0].y) + wx1 * wz0 * (v[3].y - v[1].y) + wx0 * wz1 * (v[6].y - v[4].y) + wx1 * wz1 * (v[7].y - v[5].y));
-        jz.x = s * (wx0 * wy0 * (v[4].x - v[0].x) + wx1 * wy0 * (v[5].x - v[1].x) + wx0 * wy1 * (v[6].x - v[2].x) + wx1 * wy1 * (v[7].x - v[3].x));
-        jz.y = s * (wx0 * wy0 * (v[4].y - v[0].y) + wx1 * wy0 * (v[5].y - v[1].y) + wx0 * wy1 * (v[6].y - v[2].y) + wx1 * wy1 * (v[7].y - v[3].y));
-        dydx[((size_t)l * 3 + 0) * P + p] = jx;
-        dydx[((size_t)l * 3 + 1) * P + p] = jy;
-        dydx[((size_t)l * 3 + 2) * P + p] = jz;
-      }
+      const float2 v = grid_level(table, lv, l, x, trow, dydx, P, p);
+      rmax = fmaxf(rmax, fmaxf(fabsf(v.x), fabsf(v.y)));
+      bad = bad || !(fabsf(v.x) < INFINITY) || !(fabsf(v.y) < INFINITY);
     }
   }
   const int e = plain ? 0 : sr::scale_exp(bad ? INFINITY : rmax);
@@ -342,7 +212,8 @@ __global__ __launch_bounds__(128) void encode_fwd_split_kernel(const float* __re
   //  the scaled form -- measured free beside the gather, 99.7 vs 96.0 us)
   // ---- C
   if (live) {
-    (void)oneblob_row();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) oneblob_axis_fwd(x[a], n_bins, trow + a * n_bins);
     repack(pe_dim);
   }
   flush(xs_out, ldxs_w, 0, pe_dim / 2, 0);
@@ -374,25 +245,13 @@ __global__ __launch_bounds__(128) void encode_bwd_kernel(const float* __restrict
     const uint32_t rows = min(blockDim.x, P - p0);
     const float* src = d_pe + (size_t)p0 * ld_dpe + col0;
     if (((nc | ld_dpe | col0) & 3u) == 0 && ((((uintptr_t)d_pe) & 15u) == 0)) {
-      const uint32_t nq = nc >> 2, dr = blockDim.x / nq, dc = blockDim.x - dr * nq;
-      uint32_t r = threadIdx.x / nq, c = threadIdx.x - r * nq;
-      for (uint32_t i = threadIdx.x; i < rows * nq; i += blockDim.x) {
+      tile_walk(rows, nc >> 2, [&](uint32_t r, uint32_t c) {
         const float4 v = *reinterpret_cast<const float4*>(src + (size_t)r * ld_dpe + 4 * c);
         float* t = tile + r * ldt + 4 * c;
         t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-        r += dr;
-        c += dc;
-        if (c >= nq) { c -= nq; ++r; }
-      }
+      });
     } else {
-      const uint32_t dr = blockDim.x / nc, dc = blockDim.x - dr * nc;
-      uint32_t r = threadIdx.x / nc, c = threadIdx.x - r * nc;
-      for (uint32_t i = threadIdx.x; i < rows * nc; i += blockDim.x) {
-        tile[r * ldt + c] = src[(size_t)r * ld_dpe + c];
-        r += dr;
-        c += dc;
-        if (c >= nc) { c -= nc; ++r; }
-      }
+      tile_walk(rows, nc, [&](uint32_t r, uint32_t c) { tile[r * ldt + c] = src[(size_t)r * ld_dpe + c]; });
     }
     __syncthreads();
   };
@@ -409,29 +268,9 @@ __global__ __launch_bounds__(128) void encode_bwd_kernel(const float* __restrict
   for (int a = 0; a < 3; ++a) {
     if (pe_split) stage(a * n_bins, n_bins);               // (uniform: every thread of the workgroup)
     if (live && d_pe && d_x) {
-      const float n = (float)n_bins;
-      const float* row = TILED ? tile + threadIdx.x * ldt - (pe_split ? a * n_bins : 0u) : d_pe + (size_t)p * ld_dpe;
-      const float xa = x[a];
-      if (n_bins >= 8u && fabsf(xa) < 4.0f) {
-        float accw = 0.f;
-        oneblob_windows<true>(n_bins, n, xa, [&](uint32_t j, float v) { accw -= row[a * n_bins + j] * v; });
-        dx[a] += accw;
-        continue;
-      }
-      float first = 0.f, left = 0.f, acc = 0.f;
-      for (uint32_t b = 0; b <= n_bins; ++b) {
-        float g;
-        if (b < n_bins) {
-          const float d = (float)b / n - xa;
-          g = quartic_pdf(d, n) + quartic_pdf(d - 1.0f, n) + quartic_pdf(d + 1.0f, n);
-          if (b == 0) first = g;
-        } else {
-          g = first;
-        }
-        if (b > 0) acc -= row[a * n_bins + b - 1] * (g - left);  // d out_b / dx = -(g(b+1) - g(b))
-        left = g;
-      }
-      dx[a] += acc;
+      // the axis' gradient columns: a whole row (tile or global), or the axis' own tile phase
+      const float* grad = TILED ? tile + threadIdx.x * ldt + (pe_split ? 0u : a * n_bins) : d_pe + (size_t)p * ld_dpe + a * n_bins;
+      oneblob_axis_bwd(x[a], n_bins, grad, dx[a]);
     }
   }
   for (uint32_t ph = 0; ph < (TILED ? g_ph : 1u); ++ph) {
@@ -460,13 +299,7 @@ __global__ __launch_bounds__(128) void encode_bwd_kernel(const float* __restrict
       const uint32_t off = lv.offset[l];
       float f[3];
       uint32_t g[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float pos = __fadd_rn(__fmul_rn(x[a], s), 0.5f);
-        const float fl = floorf(pos);
-        g[a] = (uint32_t)(int)fl;
-        f[a] = pos - fl;
-      }
+      grid_cell(x, s, g, f);
       uint32_t r[8];
 #pragma unroll
       for (int c = 0; c < 8; ++c)
@@ -474,7 +307,7 @@ __global__ __launch_bounds__(128) void encode_bwd_kernel(const float* __restrict
       if (d_table && (g0 != 0.f || g1 != 0.f)) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          const float w = ((c & 1) ? f[0] : 1.0f - f[0]) * ((c & 2) ? f[1] : 1.0f - f[1]) * ((c & 4) ? f[2] : 1.0f - f[2]);
+          const float w = corner_weight(f, (uint32_t)c);
           atomicAdd(d_table + 2 * (size_t)r[c], w * g0);
           atomicAdd(d_table + 2 * (size_t)r[c] + 1, w * g1);
         }
@@ -518,8 +351,8 @@ __global__ __launch_bounds__(256) void hashgrid_indices_kernel(const float* __re
   const float x[3] = {xin[(size_t)p * 3], xin[(size_t)p * 3 + 1], xin[(size_t)p * 3 + 2]};
   for (uint32_t l = 0; l < lv.n_levels; ++l) {
     uint32_t g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = (uint32_t)(int)floorf(__fadd_rn(__fmul_rn(x[a], lv.scale[l]), 0.5f));
+    float f[3];                                    // (not needed here)
+    grid_cell(x, lv.scale[l], g, f);
 #pragma unroll
     for (int c = 0; c < 8; ++c)
       rows[((size_t)p * lv.n_levels + l) * 8 + c] =

@@ -2,10 +2,11 @@
 // the partition / queue pair, the three pair-list kernels, and launch_table_scatter, which issues what a ScatterPlan
 // (scatter_plan.hpp: forms per level, workspace layout, grids and LDS sizes) says.  Called by dns_encode_bwd (encode.hip).
 //
-// Compiled like encode.hip with -ffp-contract=off: the cell and fraction of a point (pair_cell, the corner rows and weights) must
-// round exactly as the encoder's, pos = x*scale + 0.5 in two IEEE roundings.
+// Compiled like encode.hip with -ffp-contract=off: the cell, fraction and corner weights of a point are the encoder's own functions
+// (dev_encode.hpp: grid_cell, corner_weight, pair_weights), and the corner rows formed here from the cell must be the forward's.
 #include <type_traits>
 #include "common.hpp"
+#include "dev_encode.hpp"
 #include "scatter_plan.hpp"
 
 namespace dns {
@@ -104,19 +105,18 @@ __global__ __launch_bounds__(256) void dgrid_transpose_kernel(const float* __res
       for (uint32_t l = 0; l < n_levels; ++l)
         dg_t[(size_t)l * P + p] = make_float2(tile[threadIdx.x * LDT + 2 * l], tile[threadIdx.x * LDT + 2 * l + 1]);
       if (rows16) {
-        const float x0 = xin[(size_t)p * 3], x1 = xin[(size_t)p * 3 + 1], x2 = xin[(size_t)p * 3 + 2];
+        const float xc[3] = {xin[(size_t)p * 3], xin[(size_t)p * 3 + 1], xin[(size_t)p * 3 + 2]};
         for (uint32_t l = 0; l < n_levels; ++l) {
           const int slot = rp.slot[l];
           if (slot < 0) continue;                      // uniform
-          const float sc = lv.scale[l];
-          const uint32_t g0 = (uint32_t)(int)floorf(__fadd_rn(__fmul_rn(x0, sc), 0.5f));
-          const uint32_t g1 = (uint32_t)(int)floorf(__fadd_rn(__fmul_rn(x1, sc), 0.5f));
-          const uint32_t g2 = (uint32_t)(int)floorf(__fadd_rn(__fmul_rn(x2, sc), 0.5f));
+          uint32_t g[3];
+          float f[3];                                  // (only the cell is needed)
+          grid_cell(xc, lv.scale[l], g, f);
           const uint32_t mask = lv.size[l] - 1u;       // hashed levels are exactly 2^T rows (<= 2^16 here)
-          const uint32_t ay0 = g1 * 2654435761u, ay1 = ay0 + 2654435761u, az0 = g2 * 805459861u, az1 = az0 + 805459861u;
+          const uint32_t ay0 = g[1] * 2654435761u, ay1 = ay0 + 2654435761u, az0 = g[2] * 805459861u, az1 = az0 + 805459861u;
           uint32_t r[8];
 #pragma unroll
-          for (int c = 0; c < 8; ++c) r[c] = ((g0 + (uint32_t)(c & 1)) ^ ((c & 2) ? ay1 : ay0) ^ ((c & 4) ? az1 : az0)) & mask;
+          for (int c = 0; c < 8; ++c) r[c] = ((g[0] + (uint32_t)(c & 1)) ^ ((c & 2) ? ay1 : ay0) ^ ((c & 4) ? az1 : az0)) & mask;
           rows16[(size_t)slot * P + p] = make_uint4(r[0] | (r[1] << 16), r[2] | (r[3] << 16), r[4] | (r[5] << 16), r[6] | (r[7] << 16));
         }
       }
@@ -264,13 +264,7 @@ __global__ __launch_bounds__(1024) void hashgrid_bwd_binned_kernel(const float* 
       const bool work = live && !(gg.x == 0.f && gg.y == 0.f);
       float f[3];
       uint32_t g[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float pos = __fadd_rn(__fmul_rn(xc[a], s), 0.5f);
-        const float fl = floorf(pos);
-        g[a] = (uint32_t)(int)fl;
-        f[a] = pos - fl;
-      }
+      grid_cell(xc, s, g, f);
       // per-axis terms of the row index: hashed  x ^ y*P1 ^ z*P2,  dense  x + y*res + z*res^2
       const uint32_t ax0 = g[0], ax1 = g[0] + 1u;
       const uint32_t ay0 = HASHED ? g[1] * 2654435761u : g[1] * res, ay1 = ay0 + (HASHED ? 2654435761u : res);
@@ -301,8 +295,8 @@ __global__ __launch_bounds__(1024) void hashgrid_bwd_binned_kernel(const float* 
           hit_mask &= hit_mask - 1u;
           const uint32_t y = (c & 1u) ? ay1 : ay0, z = (c & 2u) ? az1 : az0;
           const uint32_t l0 = row_of(ax0, y, z) - base, l1 = row_of(ax1, y, z) - base;
-          const float wyz = ((c & 1u) ? f[1] : 1.0f - f[1]) * ((c & 2u) ? f[2] : 1.0f - f[2]);
-          const float w0 = (1.0f - f[0]) * wyz, w1 = f[0] * wyz;
+          float w0, w1;
+          pair_weights(f, c, w0, w1);
           if (l0 < rows_eff) {
             atomicAdd(dbins + 2 * l0, (double)(w0 * gg.x));
             atomicAdd(dbins + 2 * l0 + 1, (double)(w0 * gg.y));
@@ -357,13 +351,7 @@ __global__ __launch_bounds__(1024) void hashgrid_bwd_binned_kernel(const float* 
       if (!(live && !(gg.x == 0.f && gg.y == 0.f))) continue;
       float f[3];
       uint32_t g[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float pos = __fadd_rn(__fmul_rn(xc[a], s), 0.5f);
-        const float fl = floorf(pos);
-        g[a] = (uint32_t)(int)fl;
-        f[a] = pos - fl;
-      }
+      grid_cell(xc, s, g, f);
       const uint32_t r000 = g[0] + g[1] * res + g[2] * res2;
       if (r000 != cur) {
         if (in_range) flush();
@@ -375,7 +363,7 @@ __global__ __launch_bounds__(1024) void hashgrid_bwd_binned_kernel(const float* 
       if (!in_range) continue;
 #pragma unroll
       for (uint32_t c = 0; c < 8; ++c) {
-        const float w = ((c & 1u) ? f[0] : 1.0f - f[0]) * ((c & 2u) ? f[1] : 1.0f - f[1]) * ((c & 4u) ? f[2] : 1.0f - f[2]);
+        const float w = corner_weight(f, c);
         acc[c][0] += (double)(w * gg.x);
         acc[c][1] += (double)(w * gg.y);
       }
@@ -417,18 +405,15 @@ __global__ __launch_bounds__(1024) void hashgrid_bwd_binned_kernel(const float* 
       }
       if (!__any(hit_mask != 0)) continue;       // (uniform) most visits of a wave whose points miss this chunk end here
       float f[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float pos = __fadd_rn(__fmul_rn(xc[a], s), 0.5f);
-        f[a] = pos - floorf(pos);
-      }
+      uint32_t g[3];                               // (the rows are the stored ones)
+      grid_cell(xc, s, g, f);
       while (__any(hit_mask != 0)) {
         if (hit_mask) {
           const uint32_t c = (uint32_t)__ffs((int)hit_mask) - 1u;
           hit_mask &= hit_mask - 1u;
           const uint32_t wsel = (c >> 1) == 0u ? rr.x : ((c >> 1) == 1u ? rr.y : ((c >> 1) == 2u ? rr.z : rr.w));
           const uint32_t local = ((c & 1u) ? (wsel >> 16) : (wsel & 0xffffu)) - base;
-          const float w = ((c & 1u) ? f[0] : 1.0f - f[0]) * ((c & 2u) ? f[1] : 1.0f - f[1]) * ((c & 4u) ? f[2] : 1.0f - f[2]);
+          const float w = corner_weight(f, c);
           atomicAdd(dbins + 2 * local, (double)(w * gg.x));
           atomicAdd(dbins + 2 * local + 1, (double)(w * gg.y));
         }
@@ -486,13 +471,7 @@ __global__ __launch_bounds__(PART_THREADS) void hashgrid_bwd_partition_kernel(co
     const bool hashed = lv.hashed[l] != 0;       // uniform
     float f[3];
     uint32_t g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float pos = __fadd_rn(__fmul_rn(xc[a], s), 0.5f);
-      const float fl = floorf(pos);
-      g[a] = (uint32_t)(int)fl;
-      f[a] = pos - fl;
-    }
+    grid_cell(xc, s, g, f);
     // per-axis terms of the row index: hashed  x ^ y*P1 ^ z*P2 (size = 2^T),  dense  (x + y*res + z*res^2) mod size
     const uint32_t ax0 = g[0], ax1 = g[0] + 1u;
     const uint32_t ay0 = hashed ? g[1] * 2654435761u : g[1] * res, ay1 = ay0 + (hashed ? 2654435761u : res);
@@ -538,7 +517,7 @@ __global__ __launch_bounds__(PART_THREADS) void hashgrid_bwd_partition_kernel(co
     if (work) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const float w = ((c & 1) ? f[0] : 1.0f - f[0]) * ((c & 2) ? f[1] : 1.0f - f[1]) * ((c & 4) ? f[2] : 1.0f - f[2]);
+        const float w = corner_weight(f, (uint32_t)c);
         const uint32_t ch = rows8[c] >> pp.chunk_shift;
         const uint32_t at = base[ch] + slot8[c];
         st_row[at] = rows8[c] & row_mask;
@@ -627,15 +606,6 @@ struct PairRows {
   uint32_t l0, l1;
   float w0, w1;
 };
-__device__ __forceinline__ void pair_cell(const float xc[3], float s, uint32_t g[3], float f[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float pos = __fadd_rn(__fmul_rn(xc[a], s), 0.5f);
-    const float fl = floorf(pos);
-    g[a] = (uint32_t)(int)fl;
-    f[a] = pos - fl;
-  }
-}
 __device__ __forceinline__ void pair_rows_only(const uint32_t g[3], uint32_t c, bool hashed, uint32_t res, uint32_t size,
                                                uint32_t& l0, uint32_t& l1) {
   const uint32_t gy = g[1] + (c & 1u), gz = g[2] + ((c >> 1) & 1u);
@@ -655,12 +625,10 @@ __device__ __forceinline__ void pair_rows_only(const uint32_t g[3], uint32_t c, 
 __device__ __forceinline__ PairRows pair_rows(const float xc[3], float s, uint32_t c, bool hashed, uint32_t res, uint32_t size) {
   uint32_t g[3];
   float f[3];
-  pair_cell(xc, s, g, f);
+  grid_cell(xc, s, g, f);
   PairRows r;
   pair_rows_only(g, c, hashed, res, size, r.l0, r.l1);
-  const float wyz = ((c & 1u) ? f[1] : 1.0f - f[1]) * ((c & 2u) ? f[2] : 1.0f - f[2]);
-  r.w0 = (1.0f - f[0]) * wyz;
-  r.w1 = f[0] * wyz;
+  pair_weights(f, c, r.w0, r.w1);
   return r;
 }
 
@@ -702,7 +670,7 @@ __global__ __launch_bounds__(LIST_THREADS) void hashgrid_bwd_pairlist_kernel(con
     const float xc[3] = {xin[(size_t)p * 3], xin[(size_t)p * 3 + 1], xin[(size_t)p * 3 + 2]};
     uint32_t g[3];
     float f[3];
-    pair_cell(xc, s, g, f);
+    grid_cell(xc, s, g, f);
 #pragma unroll
     for (uint32_t c = 0; c < 4; ++c) {
       uint32_t l0, l1;
@@ -730,7 +698,7 @@ __global__ __launch_bounds__(LIST_THREADS) void hashgrid_bwd_pairlist_kernel(con
     const float xc[3] = {xin[(size_t)p * 3], xin[(size_t)p * 3 + 1], xin[(size_t)p * 3 + 2]};
     uint32_t g[3];
     float f[3];
-    pair_cell(xc, s, g, f);
+    grid_cell(xc, s, g, f);
 #pragma unroll
     for (uint32_t c = 0; c < 4; ++c) {
       uint32_t l0, l1;
@@ -748,8 +716,8 @@ __global__ __launch_bounds__(LIST_THREADS) void hashgrid_bwd_pairlist_kernel(con
       if (c1 != c0 && !over1) ql[(size_t)c1 * cap + at1] = (p << 2) | c;
       if (over0 || over1) {                      // list full: the pair's corners in that chunk go straight to the table
         const float2 gg = dgl[p];
-        const float wyz = ((c & 1u) ? f[1] : 1.0f - f[1]) * ((c & 2u) ? f[2] : 1.0f - f[2]);
-        const float w0 = (1.0f - f[0]) * wyz, w1 = f[0] * wyz;
+        float w0, w1;
+        pair_weights(f, c, w0, w1);
         if (over0) {
           atomicAdd(tl + 2 * (size_t)l0, w0 * gg.x);
           atomicAdd(tl + 2 * (size_t)l0 + 1, w0 * gg.y);

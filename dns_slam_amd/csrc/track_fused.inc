@@ -52,110 +52,6 @@ __device__ __forceinline__ RayLds ray_lds(lds_fp keep, uint32_t r) {
   return {b, b + 64, b + 128, b + 192, b + 208, b + 212};
 }
 
-// one level of the hash grid for one point: features -> row[2 l], row[2 l + 1], d(features)/dx -> dydx (encode_fwd_kernel's
-// arithmetic, never contracted)
-template <typename RowP>
-__device__ __forceinline__ void grid_level(const float2* __restrict__ table, const GridLevels& lv, uint32_t l, const float (&x)[3],
-                                           RowP row, float2* __restrict__ dydx, uint32_t P, uint32_t p) {
-#pragma clang fp contract(off)
-  const float s = lv.scale[l];
-  const uint32_t res = lv.resolution[l], size = lv.size[l], hashed = lv.hashed[l];
-  const float2* __restrict__ t = table + lv.offset[l];
-  float f[3];
-  uint32_t g[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float pos = __fadd_rn(__fmul_rn(x[a], s), 0.5f);
-    const float fl = floorf(pos);
-    g[a] = (uint32_t)(int)fl;
-    f[a] = pos - fl;
-  }
-  float2 v[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) v[c] = t[grid_row(g[0] + (c & 1), g[1] + ((c >> 1) & 1), g[2] + ((c >> 2) & 1), res, size, hashed)];
-  float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float w = ((c & 1) ? f[0] : 1.0f - f[0]) * ((c & 2) ? f[1] : 1.0f - f[1]) * ((c & 4) ? f[2] : 1.0f - f[2]);
-    a0 += w * v[c].x;
-    a1 += w * v[c].y;
-  }
-  row[2 * l] = a0;
-  row[2 * l + 1] = a1;
-  const float wx0 = 1.0f - f[0], wx1 = f[0], wy0 = 1.0f - f[1], wy1 = f[1], wz0 = 1.0f - f[2], wz1 = f[2];
-  float2 jx, jy, jz;
-  jx.x = s * (wy0 * wz0 * (v[1].x - v[0].x) + wy1 * wz0 * (v[3].x - v[2].x) + wy0 * wz1 * (v[5].x - v[4].x) + wy1 * wz1 * (v[7].x - v[6].x));
-  jx.y = s * (wy0 * wz0 * (v[1].y - v[0].y) + wy1 * wz0 * (v[3].y - v[2].y) + wy0 * wz1 * (v[5].y - v[4].y) + wy1 * wz1 * (v[7].y - v[6].y));
-  jy.x = s * (wx0 * wz0 * (v[2].x - v[0].x) + wx1 * wz0 * (v[3].x - v[1].x) + wx0 * wz1 * (v[6].x - v[4].x) + wx1 * wz1 * (v[7].x - v[5].x));
-  jy.y = s * (wx0 * wz0 * (v[2].y - v[0].y) + wx1 * wz0 * (v[3].y - v[1].y) + wx0 * wz1 * (v[6].y - v[4].y) + wx1 * wz1 * (v[7].y - v[5].y));
-  jz.x = s * (wx0 * wy0 * (v[4].x - v[0].x) + wx1 * wy0 * (v[5].x - v[1].x) + wx0 * wy1 * (v[6].x - v[2].x) + wx1 * wy1 * (v[7].x - v[3].x));
-  jz.y = s * (wx0 * wy0 * (v[4].y - v[0].y) + wx1 * wy0 * (v[5].y - v[1].y) + wx0 * wy1 * (v[6].y - v[2].y) + wx1 * wy1 * (v[7].y - v[3].y));
-  dydx[((size_t)l * 3 + 0) * P + p] = jx;
-  dydx[((size_t)l * 3 + 1) * P + p] = jy;
-  dydx[((size_t)l * 3 + 2) * P + p] = jz;
-}
-
-// OneBlob of one point into row[0 .. 3 n_bins) (encode_fwd_kernel's two forms)
-template <typename RowP>
-__device__ __forceinline__ void oneblob_row(const float (&x)[3], uint32_t n_bins, RowP row, int a0 = 0, int a1 = 3) {
-#pragma clang fp contract(off)
-  const float n = (float)n_bins;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (a < a0 || a >= a1) continue;         // (uniform: the axes are split over the ray's waves)
-    const float xa = x[a];
-    if (n_bins >= 8u && fabsf(xa) < 4.0f) {
-      for (uint32_t b = 0; b < n_bins; ++b) row[a * n_bins + b] = 0.f;
-      oneblob_windows<false>(n_bins, n, xa, [&](uint32_t j, float v) { row[a * n_bins + j] = v; });
-      continue;
-    }
-    float first = 0.f, left = 0.f;
-    for (uint32_t b = 0; b <= n_bins; ++b) {
-      float g;
-      if (b < n_bins) {
-        const float d = (float)b / n - xa;
-        g = quartic_cdf(d, n) + quartic_cdf(d - 1.0f, n) + quartic_cdf(d + 1.0f, n);
-        if (b == 0) first = g;
-      } else {
-        g = first + 1.0f;
-      }
-      if (b > 0) row[a * n_bins + b - 1] = g - left;
-      left = g;
-    }
-  }
-}
-
-// d OneBlob / dx contracted with the row's upstream gradient (encode_bwd_kernel's two forms)
-template <typename RowP>
-__device__ __forceinline__ void oneblob_bwd(const float (&x)[3], uint32_t n_bins, RowP row, float (&dx)[3]) {
-#pragma clang fp contract(off)
-  const float n = (float)n_bins;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float xa = x[a];
-    if (n_bins >= 8u && fabsf(xa) < 4.0f) {
-      float accw = 0.f;
-      oneblob_windows<true>(n_bins, n, xa, [&](uint32_t j, float v) { accw -= row[a * n_bins + j] * v; });
-      dx[a] += accw;
-      continue;
-    }
-    float first = 0.f, left = 0.f, acc = 0.f;
-    for (uint32_t b = 0; b <= n_bins; ++b) {
-      float g;
-      if (b < n_bins) {
-        const float d = (float)b / n - xa;
-        g = quartic_pdf(d, n) + quartic_pdf(d - 1.0f, n) + quartic_pdf(d + 1.0f, n);
-        if (b == 0) first = g;
-      } else {
-        g = first;
-      }
-      if (b > 0) acc -= row[a * n_bins + b - 1] * (g - left);
-      left = g;
-    }
-    dx[a] += acc;
-  }
-}
-
 // (anonymous namespace: every translation unit instantiates track_fused_kernel<MTL> for ITS network shape -- with external
 //  linkage the two instantiations share one mangled name and the linker keeps one of them for both launchers)
 namespace {
@@ -245,7 +141,10 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
           a.x3[(size_t)p * 3 + 1] = x[1];
           a.x3[(size_t)p * 3 + 2] = x[2];
         }
-        oneblob_row(x, a.n_bins, rowp, ax0, ax1);
+        // (OneBlob, like the grid levels below, is dev_encode.hpp's: the encoder kernels' arithmetic, never contracted)
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax)
+          if (ax >= ax0 && ax < ax1) oneblob_axis_fwd(x[ax], a.n_bins, rowp + ax * a.n_bins);
         if (part + 1u == wpr) {
           // the rows' grid columns of d_buf are only ever ADDED to (by the coarse network's backward): cleared here
           float* dg = a.d_buf + (size_t)p * ld + pe;
@@ -255,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
         const uint32_t l0 = wpr == 2u ? (part == 0u ? 0u : (3u * L) / 8u) : L * part / wpr;
         const uint32_t l1 = wpr == 2u ? (part == 0u ? (3u * L) / 8u : L) : L * (part + 1u) / wpr;
 #pragma unroll 4
-        for (uint32_t l = l0; l < l1; ++l) grid_level(a.table, a.lv, l, x, rowp + pe, a.dydx, P, p);
+        for (uint32_t l = l0; l < l1; ++l) grid_level<true, true>(a.table, a.lv, l, x, rowp + pe, a.dydx, P, p);
         if (a.n_phases == 13u) return;                // (tools: behind the grid levels)
       }
     }
@@ -515,7 +414,8 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
       const lds_fp g = tile + (p - p0) * (ld + 1u);
       if (part == 0u) {
         const float x[3] = {a.x3[(size_t)p * 3], a.x3[(size_t)p * 3 + 1], a.x3[(size_t)p * 3 + 2]};
-        oneblob_bwd(x, a.n_bins, g, dx);
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) oneblob_axis_bwd(x[ax], a.n_bins, g + ax * a.n_bins, dx[ax]);
       }
       const uint32_t l0 = L * part / wpr, l1 = L * (part + 1u) / wpr;        // (any split: the parts' sums are added)
 #pragma unroll 4
