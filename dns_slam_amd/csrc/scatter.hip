@@ -316,8 +316,10 @@ __global__ __launch_bounds__(1024) void hashgrid_bwd_binned_kernel(const float* 
   // the bins when the cell changes: one set of atomics per run instead of per point, with few lanes active at a time.
   auto sweep_dense_runs = [&]() {
     const uint32_t res2 = res * res;
-    uint32_t cur = 0xffffffffu;                  // row of the current cell's corner (0, 0, 0); a live cell never has this value
-    bool in_range = false;
+    // row of the current cell's corner (0, 0, 0), as the uint32 sum the forward forms (grid_row) BEFORE its % size: a cell below the
+    // box on some axis has coordinate 0xffffffff there and the sum wraps -- every value is a live one, hence the separate flag
+    uint32_t cur = 0u;
+    bool have = false, in_range = false;
     double acc[8][2];
 #pragma unroll
     for (int c = 0; c < 8; ++c) acc[c][0] = acc[c][1] = 0.0;
@@ -353,12 +355,14 @@ __global__ __launch_bounds__(1024) void hashgrid_bwd_binned_kernel(const float* 
       uint32_t g[3];
       grid_cell(xc, s, g, f);
       const uint32_t r000 = g[0] + g[1] * res + g[2] * res2;
-      if (r000 != cur) {
+      if (!have || r000 != cur) {
         if (in_range) flush();
         cur = r000;
-        // a cell none of whose rows can lie in this chunk (no wrap-around: the last row is below the level's size) is skipped whole
+        have = true;
+        // a cell none of whose rows can lie in this chunk is skipped whole -- decidable only where the eight sums r000 .. last
+        // neither wrap past 2^32 (last < r000: a cell outside the box) nor reach the level's size (flush takes them % size)
         const uint32_t last = r000 + 1u + res + res2;
-        in_range = last >= size || (last >= base && r000 < base + rows);
+        in_range = last < r000 || last >= size || (last >= base && r000 < base + rows);
       }
       if (!in_range) continue;
 #pragma unroll
