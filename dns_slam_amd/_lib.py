@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class DnsGridMeta(C.Structure):
@@ -150,6 +150,12 @@ SIGNATURES = {
     "dns_point_masks_ws_bytes": (C.c_uint64, [_U, _U, _U]),
     "dns_point_masks": (C.c_int, [_P, _U, _P, _U, _P, _P, _U, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
     "dns_kf_code_mean": (C.c_int, [_P, _U, C.c_uint64, _P, _P, _U, _U, _P, _P]),
+    "dns_tsdf_touch": (C.c_int, [_P, _P, _U, _I, _I, _I, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _U, _P, _P]),
+    "dns_tsdf_integrate": (C.c_int, [_P, _U, _P, _P, _P, _P, _P, _U, _I, _I, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P]),
+    "dns_tsdf_vertex_count": (C.c_int, [_P, _U, _P, _P, _P, _P]),
+    "dns_tsdf_vertex_emit": (C.c_int, [_P, _U, _P, _P, C.c_double, _P, _P, C.c_uint64, _P]),
+    "dns_convex_hull_ws_bytes": (C.c_uint64, [_U, _U]),
+    "dns_convex_hull": (C.c_int, [_P, _U, C.c_double, _P, _U, _P, _P, C.POINTER(_U), C.POINTER(C.c_double), _P]),
 }
 
 

@@ -13,9 +13,14 @@ pass, marching cubes, cleaning and the component filter are the same with and wi
 ``ops.point_masks``) with its depth test and its all-frames branch; ``forecast=True`` is the reference's ``show_forecast`` mesh
 (fine decoders on the seen part of the grid, the coarse network on the forecast band, -100 elsewhere) and ``depth_test=True`` its
 ``meshing.depth_test`` cleaning.
+
+``Mesher.get_bound_from_frames`` is the reference's scene bound (meshing.py:380-445): the keyframes' depth images fused into a TSDF
+(csrc/tsdf.hip, ``ops.tsdf_fuse`` / ``ops.tsdf_vertices``), the convex hull of its vertices and the camera centres (csrc/hull.hip,
+``ops.convex_hull``), scaled by ``clean_mesh_bound_scale``; ``bound_planes="frames"`` hands it to the forecast mesh's cleaning.
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import numpy as np
@@ -24,9 +29,30 @@ import torch
 from . import ops
 
 
+Bound = collections.namedtuple("Bound", "verts faces planes")
+Bound.__doc__ = """Mesher.get_bound_from_frames: verts [h,3] float64 (the scaled hull's vertices), faces [F,3] int64 into verts (outward
+orientation), planes [F,4] float64 (unit outward n, d; inside is n . x + d <= 0: what ``inside_planes`` consumes)."""
+
+
+def open3d_poses(keyframe_dict):
+    """The keyframes' poses as the reference hands them to Open3D (meshing.py:409-414), on the host in float64: est_c2w keeps its
+    float32 values, columns 1 and 2 of the rotation are negated (this project's cameras look along -z, Open3D's along +z) -- on a
+    COPY: the reference negates in place on a view that can alias the keyframe's own CPU tensor --, the extrinsic is its inverse
+    and the back-projection pose the inverse of that.  -> (extrinsic [K,4,4], pose [K,4,4], centres [K,3]), numpy float64."""
+    K = len(keyframe_dict)
+    c = np.zeros((K, 4, 4), np.float64)
+    for k, kf in enumerate(keyframe_dict):
+        c[k] = torch.as_tensor(kf["est_c2w"]).detach().cpu().numpy().astype(np.float32).astype(np.float64)
+    c[:, :3, 1] *= -1.0
+    c[:, :3, 2] *= -1.0
+    ext = np.stack([np.linalg.inv(c[k]) for k in range(K)]) if K else np.zeros((0, 4, 4))
+    pose = np.stack([np.linalg.inv(ext[k]) for k in range(K)]) if K else np.zeros((0, 4, 4))
+    return ext, pose, c[:, :3, 3].copy()
+
+
 class Mesher:
     """``Mesher(cfg, slam)`` of the reference for one ``mapping.Mapper``.  Reads ``cfg['meshing']`` (resolution, level_set,
-    points_batch_size, clean_mesh, remove_small_geometry_threshold), ``cfg['scale']`` (default 1) and
+    points_batch_size, clean_mesh, clean_mesh_bound_scale (default 1.02), remove_small_geometry_threshold), ``cfg['scale']`` (default 1) and
     ``cfg['back_end']['marching_cubes_bound']`` (default: the mapper's bound).
 
     The reference always filters the cleaned mesh by connected components; here that is asked for per call: a reference config
@@ -41,6 +67,7 @@ class Mesher:
         self.level_set = float(m["level_set"])
         self.points_batch_size = int(m["points_batch_size"])
         self.clean_mesh = bool(m.get("clean_mesh", True))
+        self.clean_mesh_bound_scale = float(m.get("clean_mesh_bound_scale", 1.02))
         self.scale = float(cfg.get("scale", 1))
         thr = m.get("remove_small_geometry_threshold")
         self.remove_small_geometry_threshold = None if thr is None else float(thr)
@@ -164,7 +191,55 @@ class Mesher:
         return out if out is not None else torch.zeros(0, 1, 1, 64, device=self.device)
 
     @torch.no_grad()
-    def grid_occupancy(self, keyframe_dict, stage="fine", kf=None, stem=None, forecast=False, depth_test=False, all_frames=None):
+    def get_bound_from_frames(self, keyframe_dict, scale=None, *, voxel_length=None, sdf_trunc=None, stride=4, hull_eps=0.0):
+        """The reference's scene bound (meshing.py:380-445) -> ``Bound(verts, faces, planes)`` on the device, in the scaled units
+        ``extract`` works in.  The keyframes' gt_depth images are fused into a TSDF under ``open3d_poses`` (``ops.tsdf_fuse``:
+        voxel_length 4 scale / 512, sdf_trunc 0.04 scale, every ``stride``-th pixel deciding which 16^3 units a frame touches --
+        the reference's parameters and Open3D's; ``scale`` defaults to ``self.scale``); the points are the camera centres followed
+        by the vertices of its zero crossing (``ops.tsdf_vertices``); their convex hull (``ops.convex_hull``) is scaled by
+        ``clean_mesh_bound_scale`` about the mean c of its vertices, which turns a face (n, d) into (n, s d + (s - 1) n . c).
+
+        ``hull_eps`` is the hull's tolerance and 0 by default.  A tolerance (voxel_length / 128, say) would under-approximate the
+        points by at most that much, harmless beside a bound grown by 2 % of a metre-sized room -- but it also drops the hull
+        vertices that protrude by less, and the reference scales about the MEAN OF THE HULL'S VERTICES, which then moves: on the
+        synthetic test scene 150 vertices instead of 219 shift c by 0.69 m and the planes by up to 1.4 cm, for 146 rounds
+        instead of 215.  The exact hull is what the reference builds, so it is the default.  The keyframes are not modified."""
+        sc = self.scale if scale is None else float(scale)
+        vl = 4.0 * sc / 512.0 if voxel_length is None else float(voxel_length)
+        tr = 0.04 * sc if sdf_trunc is None else float(sdf_trunc)
+        dev = self.device
+        ext, pose, centres = open3d_poses(keyframe_dict)
+        if len(keyframe_dict) == 0:
+            raise ValueError("Mesher.get_bound_from_frames: keyframe_dict is empty")
+        depths = torch.stack([torch.as_tensor(kf["gt_depth"]).to(dev).float() for kf in keyframe_dict]).contiguous()
+        units, tsdf, weight = ops.tsdf_fuse(depths, torch.from_numpy(ext).to(dev), torch.from_numpy(pose).to(dev), self.cam, vl, tr, stride)
+        verts = ops.tsdf_vertices(units, tsdf, weight, vl)
+        points = torch.cat((torch.from_numpy(centres).to(dev), verts))
+        vi, faces, planes, _ = ops.convex_hull(points, eps=float(hull_eps))
+        hv = points[vi]
+        c = hv.mean(0)
+        s = self.clean_mesh_bound_scale
+        n = planes[:, :3]
+        nc = (n[:, 0] * c[0] + n[:, 1] * c[1]) + n[:, 2] * c[2]
+        scaled = torch.cat((n, (s * planes[:, 3] + (s - 1.0) * nc)[:, None]), 1)
+        new_id = torch.full((points.shape[0],), -1, dtype=torch.int64, device=dev)
+        new_id[vi] = torch.arange(vi.numel(), device=dev)
+        return Bound(c + s * (hv - c), new_id[faces], scaled)
+
+    def _bound_planes(self, bound_planes, keyframe_dict, build=True):
+        """``bound_planes`` of extract / get_mesh / grid_occupancy as planes [M,4]: an array, a ``Bound``, or "frames" = the
+        reference's own bound, ``get_bound_from_frames(keyframe_dict).planes`` (built only with ``build``)."""
+        if isinstance(bound_planes, str):
+            if bound_planes != "frames":
+                raise ValueError(f"Mesher: bound_planes must be an [M,4] array of half-spaces, a Bound or \"frames\", got {bound_planes!r}")
+            return self.get_bound_from_frames(keyframe_dict).planes if build else bound_planes
+        if isinstance(bound_planes, Bound):
+            return bound_planes.planes
+        return bound_planes
+
+    @torch.no_grad()
+    def grid_occupancy(self, keyframe_dict, stage="fine", kf=None, stem=None, forecast=False, depth_test=False, all_frames=None,
+                       bound_planes=None):
         """[nx, ny, nz] occupancy volume of the query grid (meshing.py:643-654: keyframe labels -> eval_points per
         points_batch_size chunk -> values[:, 3]) and the grid's axes.  ``stem`` only lifts the refusal of a mapper with an
         encoder and is not used: the reference computes get_2d_feature's codes for every grid chunk, but they reach only the
@@ -175,8 +250,10 @@ class Mesher:
         as in ``point_masks``, taken per points_batch_size chunk of the grid); the seen points, compacted, get their keyframe
         labels and the fine decoders of ``stage`` -- the > 1 point rule per points_batch_size chunk of the COMPACTED points, as
         the reference's loop over ``points[seen_mask]`` has it --, the compacted forecast points the coarse network, the unseen
-        points -100."""
+        points -100.  ``bound_planes`` is accepted in ``extract``'s spellings ("frames" included) and checked, nothing more: the
+        reference's grid pass does not read the bound, only the cleaning of the forecast mesh does."""
         self._check_supported(stem)
+        self._bound_planes(bound_planes, keyframe_dict, build=False)
         kf = kf or self._keyframes(keyframe_dict)
         grid = self.get_grid_uniform()
         nx, ny, nz = (len(a) for a in grid["xyz"])
@@ -221,13 +298,15 @@ class Mesher:
         are those of get_mask_use_all_frames.  ``forecast`` (the reference's show_forecast): the volume of
         ``grid_occupancy(forecast=True)``; the cleaning (meshing.py:695-708) drops the faces whose three vertices all lie outside
         a convex bound, ``bound_planes`` [M,4]: a point x is inside when n . x + d <= 0 for every row (n, d) -- exactly
-        ``scipy.spatial.ConvexHull(...).equations``, in the scaled units of the marching-cubes bound; the reference's own bound,
-        get_bound_from_frames (a TSDF fusion of the keyframes and its hull), is not rebuilt, so ``forecast`` with ``clean_mesh``
-        and no ``bound_planes`` is refused.  The vertices whose mask is forecast are coloured (0, 255, 255) (:756-762)."""
+        ``scipy.spatial.ConvexHull(...).equations``, in the scaled units of the marching-cubes bound.  ``bound_planes="frames"`` is the
+        reference's own bound, ``get_bound_from_frames(keyframe_dict).planes`` (a TSDF fusion of the keyframes and its scaled hull);
+        it is never built unasked, so ``forecast`` with ``clean_mesh`` and no ``bound_planes`` is refused.  The vertices whose mask
+        is forecast are coloured (0, 255, 255) (:756-762)."""
         self._check_supported(stem)
         if forecast and clean_mesh and bound_planes is None:
-            raise NotImplementedError("Mesher.extract: forecast=True with clean_mesh=True needs bound_planes= (the half-spaces of a "
-                                      "convex bound); the reference's get_bound_from_frames is not implemented")
+            raise NotImplementedError("Mesher.extract: forecast=True with clean_mesh=True needs a bound: bound_planes=\"frames\" builds the "
+                                      "reference's (Mesher.get_bound_from_frames), or pass the half-spaces [M,4] of a convex bound")
+        self._bound_planes(bound_planes, keyframe_dict, build=False)
         if components not in (None, "small", "largest"):
             raise ValueError(f"Mesher.extract: components must be None, 'small' or 'largest', got {components!r}")
         if components is not None and not clean_mesh:
@@ -237,6 +316,7 @@ class Mesher:
                 raise ValueError("Mesher.extract: components='small' needs cfg['meshing']['remove_small_geometry_threshold'] "
                                  "(or min_area=)")
             min_area = self.remove_small_geometry_threshold * self.scale * self.scale
+        bound_planes = self._bound_planes(bound_planes, keyframe_dict, build=forecast and clean_mesh)
         kf = self._keyframes(keyframe_dict, stem)
         vol, grid = self.grid_occupancy(keyframe_dict, stage, kf, stem, forecast, depth_test, all_frames)
         x, y, z = grid["xyz"]
@@ -313,12 +393,12 @@ class Mesher:
         with ``label`` and a ``palette`` (class -> RGB: an [n_class, 3] array, a dict or a callable like the reference's
         v_map_function), ``mesh_{idx}_semantic.ply``.  Returns the paths written.  ``components`` / ``min_area``: the
         connected-components filter of ``extract`` (meshing.py:721-733); ``stem``, ``forecast`` (the reference's show_forecast),
-        ``depth_test``, ``all_frames`` and ``bound_planes``: as in ``extract``.  fill_holes (meshing.py:770) is not implemented and,
+        ``depth_test``, ``all_frames`` and ``bound_planes`` ("frames" included): as in ``extract``.  fill_holes (meshing.py:770) is not implemented and,
         like the reference's own spellings of the filters, of the forecast mesh and of the per-class meshes, refused when asked
         for."""
         if show_forecast:
-            raise NotImplementedError("Mesher.get_mesh: show_forecast is not a keyword here; pass forecast=True (with bound_planes= "
-                                      "when the mesh is cleaned)")
+            raise NotImplementedError("Mesher.get_mesh: show_forecast is not a keyword here; pass forecast=True (with "
+                                      "bound_planes=\"frames\" when the mesh is cleaned)")
         if element:
             raise NotImplementedError("Mesher.get_mesh: element is not a keyword here; the per-class meshes are written by "
                                       "Mesher.get_part_meshes")

@@ -1592,3 +1592,184 @@ def views_see_any(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: f
     check(lib.dns_views_see_any(ptr(pts), int(pts.shape[0]), ptr(w), K, int(H), int(W), _intrinsics(fx, fy, cx, cy), ptr(sees),
                                 stream_ptr()), "dns_views_see_any")
     return sees.bool()
+
+
+# ----------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)
+TSDF_UNIT = 16
+
+
+def tsdf_multiplier(H: int, W: int, cam: dict) -> np.ndarray:
+    """[H,W] fp32: the camera-distance multiplier sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1) of pixel (v, u), evaluated in
+    float64 on the host (numpy: correctly rounded division and square root) and rounded to fp32 once."""
+    u = (np.arange(W, dtype=np.float64) - float(cam["cx"])) / float(cam["fx"])
+    v = (np.arange(H, dtype=np.float64) - float(cam["cy"])) / float(cam["fy"])
+    return np.sqrt((u * u)[None, :] + (v * v)[:, None] + 1.0).astype(np.float32)
+
+
+def _tsdf_intrinsics(cam):
+    return (C.c_double * 4)(float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]))
+
+
+def tsdf_fuse(depths: torch.Tensor, extrinsic: torch.Tensor, pose: torch.Tensor, cam: dict, voxel_length: float, sdf_trunc: float,
+              stride: int = 4, *, table_slots: Optional[int] = None):
+    """TSDF fusion of K posed depth images into units of 16^3 voxels (Open3D's ScalableTSDFVolume.integrate per frame, as
+    tests/tsdf_ref.py restates it; include/dns_hip.h states every expression).  depths [K,H,W] fp32; extrinsic [K,4,4] float64
+    world->camera and pose [K,4,4] float64 = its inverse, both in Open3D's convention (the camera looks along +z); cam
+    {'fx','fy','cx','cy'}.  -> (units [B,3] int32, lexicographically sorted; tsdf [B,16,16,16] fp32; weight [B,16,16,16] fp32).
+    Frame k is integrated only into the units its pixels (every ``stride``-th row and column, 0 < depth < 1000) touch, in
+    ascending k.  No float atomics: the same bits for every call, and for every ``table_slots`` (the first size of the key table;
+    a table that turns out too small is doubled and the pass repeated).  One host read per attempt."""
+    for name, t, dt in (("depths", depths, torch.float32), ("extrinsic", extrinsic, torch.float64), ("pose", pose, torch.float64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"tsdf_fuse: {name} must be a {dt} tensor")
+        if not t.is_cuda:
+            raise ValueError(f"tsdf_fuse: {name} must be on the GPU (there is no CPU fallback)")
+    if depths.dim() != 3:
+        raise ValueError(f"tsdf_fuse: depths must be [K,H,W], got {tuple(depths.shape)}")
+    K, H, W = (int(s) for s in depths.shape)
+    for name, t in (("extrinsic", extrinsic), ("pose", pose)):
+        if tuple(t.shape) != (K, 4, 4):
+            raise ValueError(f"tsdf_fuse: {name} must be [{K},4,4], got {tuple(t.shape)}")
+    if K > 65535:
+        raise ValueError(f"tsdf_fuse: depths holds {K} keyframes; at most 65535 (the frame is 16 bits of a key)")
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError(f"tsdf_fuse: stride must be >= 1, got {stride}")
+    vl, tr = float(voxel_length), float(sdf_trunc)
+    if not (vl > 0 and tr > 0 and math.isfinite(vl) and math.isfinite(tr) and 2 * tr < TSDF_UNIT * vl):
+        raise ValueError(f"tsdf_fuse: voxel_length and sdf_trunc must be positive with 2 sdf_trunc < 16 voxel_length, got {vl}, {tr}")
+    dev = depths.device
+    dep, ext, pos = depths.detach().contiguous(), extrinsic.detach().contiguous(), pose.detach().contiguous()
+    empty = (torch.zeros(0, 3, dtype=torch.int32, device=dev), torch.zeros(0, 16, 16, 16, device=dev), torch.zeros(0, 16, 16, 16, device=dev))
+    if K == 0 or H == 0 or W == 0:
+        return empty
+    intr = _tsdf_intrinsics(cam)
+    n_samples = K * ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+    cap = int(table_slots) if table_slots is not None else max(4096, min(n_samples, 1 << 26))
+    if cap < 8:
+        raise ValueError(f"tsdf_fuse: table_slots must be >= 8, got {cap}")
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    while True:
+        if cap >= 1 << 31:
+            raise ValueError("tsdf_fuse: depths touch more than 2^31 (unit, frame) pairs")
+        table = torch.empty(cap, dtype=torch.int64, device=dev)
+        check(lib.dns_tsdf_touch(ptr(dep), ptr(pos), K, H, W, stride, intr, vl, tr, ptr(table), cap, ptr(status), stream_ptr()),
+              "dns_tsdf_touch")
+        st = int(status.item())
+        if st & 2:
+            raise ValueError("tsdf_fuse: pose / voxel_length put a unit index outside 16 bits (|coordinate| >= 32768 * 16 * voxel_length)")
+        if not st & 1:
+            break
+        cap *= 2
+    keys = torch.sort(table[table != -1]).values
+    if keys.numel() == 0:
+        return empty
+    uniq, counts = torch.unique_consecutive(keys >> 16, return_counts=True)
+    frames = (keys & 0xFFFF).to(torch.int32)
+    offset = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=dev)
+    offset[1:] = torch.cumsum(counts, 0)
+    units = torch.stack((uniq >> 32, ((uniq >> 16) & 0xFFFF) - 32768, (uniq & 0xFFFF) - 32768), 1).to(torch.int32).contiguous()
+    B = int(units.shape[0])
+    if B > 1 << 20:                                                  # 2^32 voxels, 32 GiB of tsdf and weight
+        raise ValueError(f"tsdf_fuse: voxel_length gives {B} units of 16^3 voxels (at most 2^20)")
+    mult = torch.from_numpy(tsdf_multiplier(H, W, cam)).to(dev)
+    tsdf = torch.empty(B, 16, 16, 16, device=dev)
+    weight = torch.empty(B, 16, 16, 16, device=dev)
+    check(lib.dns_tsdf_integrate(ptr(units), B, ptr(offset), ptr(frames), ptr(dep), ptr(ext), ptr(mult), K, H, W, intr, vl, tr, ptr(tsdf),
+                                 ptr(weight), stream_ptr()), "dns_tsdf_integrate")
+    return units, tsdf, weight
+
+
+def tsdf_vertices(units: torch.Tensor, tsdf: torch.Tensor, weight: torch.Tensor, voxel_length: float) -> torch.Tensor:
+    """The vertices of the TSDF's zero crossing (Open3D's extract_triangle_mesh().vertices; faces are not built): units [B,3] int32
+    sorted as ``tsdf_fuse`` returns them, tsdf / weight [B,16,16,16] fp32 -> [V,3] float64, ordered by unit, voxel, axis, without
+    duplicates.  One host read (the total)."""
+    for name, t, dt in (("units", units, torch.int32), ("tsdf", tsdf, torch.float32), ("weight", weight, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"tsdf_vertices: {name} must be a {dt} tensor")
+        if not t.is_cuda:
+            raise ValueError(f"tsdf_vertices: {name} must be on the GPU (there is no CPU fallback)")
+    if units.dim() != 2 or units.shape[1] != 3:
+        raise ValueError(f"tsdf_vertices: units must be [B,3], got {tuple(units.shape)}")
+    B = int(units.shape[0])
+    for name, t in (("tsdf", tsdf), ("weight", weight)):
+        if tuple(t.shape) != (B, 16, 16, 16):
+            raise ValueError(f"tsdf_vertices: {name} must be [{B},16,16,16], got {tuple(t.shape)}")
+    vl = float(voxel_length)
+    if not (vl > 0 and math.isfinite(vl)):
+        raise ValueError(f"tsdf_vertices: voxel_length must be positive, got {vl}")
+    dev = units.device
+    if B == 0:
+        return torch.zeros(0, 3, dtype=torch.float64, device=dev)
+    u, t, w = units.detach().contiguous(), tsdf.detach().contiguous(), weight.detach().contiguous()
+    if B > 1:
+        key = (u[:, 0].long() << 32) | ((u[:, 1].long() + 32768) << 16) | (u[:, 2].long() + 32768)
+        if bool((u.abs().max() > 32767)) or not bool((key[1:] > key[:-1]).all()):
+            raise ValueError("tsdf_vertices: units must be distinct, sorted lexicographically and within 16 bits (as tsdf_fuse returns them)")
+    count = torch.empty(B, dtype=torch.int64, device=dev)
+    check(lib.dns_tsdf_vertex_count(ptr(u), B, ptr(t), ptr(w), ptr(count), stream_ptr()), "dns_tsdf_vertex_count")
+    incl = torch.cumsum(count, 0)
+    V = int(incl[-1].item())
+    verts = torch.empty(V, 3, dtype=torch.float64, device=dev)
+    if V:
+        offset = (incl - count).contiguous()
+        check(lib.dns_tsdf_vertex_emit(ptr(u), B, ptr(t), ptr(w), vl, ptr(offset), ptr(verts), V, stream_ptr()), "dns_tsdf_vertex_emit")
+    return verts
+
+
+# ----------------------------------------------------------------------------- convex hull (csrc/hull.hip)
+def convex_hull_launch(points: torch.Tensor, eps: float = 0.0, face_cap: Optional[int] = None):
+    """``convex_hull`` with its bookkeeping: -> (faces [F,3] int64, planes [F,4] float64, info) with info = {'max_outside',
+    'rounds', 'sweeps', 'scale', 'face_cap'}.  ``face_cap`` bounds the faces ever made (replaced ones included); too small a bound
+    is quadrupled and the hull rebuilt."""
+    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("convex_hull: points must be a float32 or float64 tensor")
+    if not points.is_cuda:
+        raise ValueError("convex_hull: points must be on the GPU (there is no CPU fallback)")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"convex_hull: points must be [N,3], got {tuple(points.shape)}")
+    N = int(points.shape[0])
+    if N < 4:
+        raise ValueError(f"convex_hull: points holds {N} points; a hull in 3-D needs at least 4")
+    if N >= 1 << 31:
+        raise ValueError(f"convex_hull: points holds {N} points (must be < 2^31)")
+    eps = float(eps)
+    if not (eps >= 0 and math.isfinite(eps)):
+        raise ValueError(f"convex_hull: eps must be finite and >= 0, got {eps}")
+    pts = points.detach().double().contiguous()
+    if not bool(torch.isfinite(pts).all()):
+        raise ValueError("convex_hull: points must be finite")
+    cap = int(face_cap) if face_cap is not None else 1 << 14
+    if cap < 4:
+        raise ValueError(f"convex_hull: face_cap must be >= 4, got {cap}")
+    st = stream_ptr()
+    while True:
+        ws_b = int(_rawlib.dns_convex_hull_ws_bytes(N, cap))
+        if ws_b == 0:
+            raise ValueError(f"convex_hull: the hull of points needs more than {cap} faces")
+        ws = torch.empty(ws_b, dtype=torch.uint8, device=pts.device)
+        faces = np.empty((cap, 3), np.int32)
+        planes = np.empty((cap, 4), np.float64)
+        nf = C.c_uint32(0)
+        info = (C.c_double * 4)()
+        rc = lib.dns_convex_hull(ptr(pts), N, eps, ptr(ws), cap, C.c_void_p(faces.ctypes.data), C.c_void_p(planes.ctypes.data), C.byref(nf),
+                                 info, st)
+        if rc != 1:
+            break
+        cap *= 4
+    check(rc, "dns_convex_hull")
+    F = int(nf.value)
+    return (torch.from_numpy(faces[:F].astype(np.int64)).to(pts.device), torch.from_numpy(planes[:F].copy()).to(pts.device),
+            {"max_outside": float(info[0]), "rounds": int(info[1]), "sweeps": int(info[2]), "scale": float(info[3]), "face_cap": cap})
+
+
+def convex_hull(points: torch.Tensor, eps: float = 0.0):
+    """The convex hull of points [N,3] (float64, or float32 widened) by quickhull in float64 -> (vertex_index [h] int64 ascending:
+    the points that are hull vertices; faces [F,3] int64 into points, outward orientation; planes [F,4] float64: unit outward
+    normal n and d, a point is inside when n . x + d <= 0 for every row, which is what ``meshing.inside_planes`` consumes;
+    max_outside: the MEASURED maximum of n . x + d over all points and faces).  A face sees a point above ``eps`` (+ 1e-12 of the
+    largest coordinate), so the hull under-approximates by at most that much and skips the points that would move it by less.
+    Fewer than 4 points, or points within eps of one plane, are a ValueError.  The call reads 40 bytes back and synchronises once
+    per inserted point: it cannot be captured into a graph (csrc/hull_topology.hpp)."""
+    faces, planes, info = convex_hull_launch(points, eps)
+    return torch.unique(faces.reshape(-1)), faces, planes, info["max_outside"]

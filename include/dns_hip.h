@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 20
+#define DNS_ABI_VERSION 21
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -847,6 +847,50 @@ int dns_kf_code_mean(const float* latents, uint32_t ld_lat, uint64_t n, const in
 uint64_t dns_point_masks_ws_bytes(uint32_t P, uint32_t K, uint32_t chunk);
 int dns_point_masks(const float* pts, uint32_t P, const float* w2c, uint32_t K, const float* max_depth, const float* depths,
                     uint32_t chunk, int H, int W, const float* intr, void* ws, uint8_t* cls, void* stream);
+
+/* ---- TSDF fusion of posed depth images (the volume of get_bound_from_frames, slams/meshing.py:380-445; csrc/tsdf.hip; ABI v21) --
+ * Open3D's ScalableTSDFVolume as tests/tsdf_ref.py restates it: units of 16^3 voxels of edge voxel_length, unit (ux, uy, uz)
+ * covering [16 u voxel_length, 16 (u + 1) voxel_length) per axis.  intr [host, 4 doubles] = fx, fy, cx, cy.
+ *   dns_tsdf_touch: depth [K,H,W] fp32, pose [K,16] float64 row-major camera->world (Open3D's convention: the camera looks along
+ *     +z).  Every pixel (i, j) with i % stride == 0, j % stride == 0 and 0 < depth < 1000 is back-projected in float64 and touches
+ *     the units floor((p - sdf_trunc) / L) .. floor((p + sdf_trunc) / L) per axis, L = 16 voxel_length (2 sdf_trunc < L required).
+ *     table [cap] uint64 receives the distinct (unit, frame) keys -- (int16 ux) << 48 | (uy + 32768) << 32 | (uz + 32768) << 16 |
+ *     frame, so that their order as SIGNED 64-bit integers is the lexicographic order of (ux, uy, uz, frame) -- in unspecified
+ *     slots, all-ones elsewhere (the library presets it).  status [1]: bit 0 = the table was too small (retry with a larger one;
+ *     the table's content is then incomplete), bit 1 = a unit index outside 16 bits.  K <= 65535.
+ *   dns_tsdf_integrate: units [B,3] int32 and, for unit b, its frames frames[offset[b] .. offset[b+1]) (offset [B+1] int64) in the
+ *     order to integrate them.  extrinsic [K,16] float64 world->camera is rounded to fp32; mult [H,W] fp32 is the camera-distance
+ *     multiplier sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1).  The voxel centre (i + 0.5) voxel_length + 16 u voxel_length is
+ *     rounded to fp32 and transformed in fp32; with z > 0, u = x fx / z + cx + 0.5 (v likewise) must satisfy 1e-4 <= u < W - 1e-4;
+ *     with d = depth[(int)v, (int)u] the update applies when d > 0 and sdf = (d - z) mult > -sdf_trunc: t = min(1, sdf / sdf_trunc),
+ *     tsdf = (tsdf w + t) / (w + 1), w += 1.  tsdf, weight [B,16,16,16] fp32 (x, y, z), 16-byte aligned, are written once each.
+ *   dns_tsdf_vertex_count / dns_tsdf_vertex_emit: units sorted in the key order above.  Voxel a and axis e emit one vertex when a
+ *     and a + e are observed (weight > 0) with different (tsdf < 0) and at least one of the four cubes around that edge has eight
+ *     observed corners, looking into neighbouring units (a missing unit is unobserved): float64 0.5 voxel_length + voxel_length
+ *     index, plus |f_a| voxel_length / (|f_a| + |f_b|) along e.  count [B] int64 per unit; offset [B] = its exclusive prefix (the
+ *     caller's); verts [capacity,3] float64 ordered by unit, voxel ((x 16 + y) 16 + z), axis.  Nothing is stored at or beyond capacity.
+ * No float atomics: the same bits for every call. */
+int dns_tsdf_touch(const float* depth, const double* pose, uint32_t K, int H, int W, int stride, const double* intr,
+                   double voxel_length, double sdf_trunc, uint64_t* table, uint32_t cap, uint32_t* status, void* stream);
+int dns_tsdf_integrate(const int32_t* units, uint32_t B, const int64_t* offset, const int32_t* frames, const float* depth,
+                       const double* extrinsic, const float* mult, uint32_t K, int H, int W, const double* intr,
+                       double voxel_length, double sdf_trunc, float* tsdf, float* weight, void* stream);
+int dns_tsdf_vertex_count(const int32_t* units, uint32_t B, const float* tsdf, const float* weight, int64_t* count, void* stream);
+int dns_tsdf_vertex_emit(const int32_t* units, uint32_t B, const float* tsdf, const float* weight, double voxel_length,
+                         const int64_t* offset, double* verts, uint64_t capacity, void* stream);
+
+/* ---- 3-D convex hull (quickhull; csrc/hull.hip, csrc/hull_topology.hpp; ABI v21) ---------------------------------------------
+ * points [N,3] float64 on the device.  Face f sees a point when n_f . x + d_f > eps + 1e-12 L (L = the largest absolute
+ * coordinate; hull_topology.hpp states the algorithm and its degeneracy policy).  HOST outputs: faces_out [face_cap,3] int32
+ * (indices into points, outward orientation), planes_out [face_cap,4] float64 (unit outward n, d: inside is n . x + d <= 0),
+ * *n_faces_out, info [4] = the measured maximum of n . x + d over all points and faces, rounds, sweeps, L.  ws: device memory of
+ * dns_convex_hull_ws_bytes(N, face_cap) bytes (0 = refused), face_cap bounding the faces ever made, replaced ones included.
+ * Returns DNS_OK; 1 when face_cap was too small (retry with a larger one); DNS_E_ARG for fewer than 4 points or points within
+ * eps of one plane; DNS_E_STATE on a capturing stream or when the topology could not be kept (never a face with a zero normal).
+ * The call synchronises the stream once per round and is NOT graph-capturable. */
+uint64_t dns_convex_hull_ws_bytes(uint32_t N, uint32_t face_cap);
+int dns_convex_hull(const double* points, uint32_t N, double eps, void* ws, uint32_t face_cap, int32_t* faces_out,
+                    double* planes_out, uint32_t* n_faces_out, double* info, void* stream);
 
 #ifdef __cplusplus
 }
