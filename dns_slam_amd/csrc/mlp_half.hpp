@@ -92,14 +92,19 @@ __device__ __forceinline__ half8 pack_half(const f32x16& a) {
 }
 
 // ---- packed 16-bit helpers (VOP3P: one instruction per two values) -------------------------------------------------------
-// ReLU on packed f16 as SIGNED 16-bit integers: a negative float (sign bit set, -0 included) is a negative integer, a
-// non-negative one keeps its bits -- max(x, 0) is exactly relu, and f16(relu(v)) == relu(f16(v)) (rounding keeps the sign).
+// ReLU on packed f16 that keeps a NaN of either sign: IEEE 754-2019 maximum (gfx950's v_pk_maximum3_f16, one instruction per two
+// values); f16(relu(v)) == relu(f16(v)) (rounding keeps the sign; -0 -> +0).  A signed 16-bit integer max is relu for every
+// number too, but zeroes a NaN whose sign bit is set -- and the NaNs the matrix instructions produce (from a NaN operand, or
+// Inf - Inf) have it set (tests/test_gpu_mlp_range.py).
 __device__ __forceinline__ uint32_t pk_relu(uint32_t x) {
-  uint32_t r;
-  asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(x));
-  return r;
+  typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+  half2v v = *reinterpret_cast<const half2v*>(&x);
+  const half2v z = {(_Float16)0, (_Float16)0};
+  v = __builtin_elementwise_maximum(v, z);
+  return *reinterpret_cast<const uint32_t*>(&v);
 }
 // ReLU' mask of two ACTIVATIONS (relu-ed f16: bits >= 0 as signed integers): 0xffff per half whose activation is > 0
+// (a NaN activation: by its sign bit -- either way the point's outputs are already NaN)
 __device__ __forceinline__ uint32_t pk_pos_mask(uint32_t act) {
   uint32_t n, m;
   asm("v_pk_sub_i16 %0, 0, %1" : "=v"(n) : "v"(act));          // -bits: negative exactly where the activation is non-zero

@@ -20,7 +20,18 @@
 // Scaling: f16 has 30 binades of normal range, so every operand is scaled by a power of two that puts its largest
 // magnitude in [2^13, 2^14): weights per matrix (workgroup-wide max when the LDS images are built), activations and
 // gradients PER POINT (a lane pair's max; the scale factors out of the point's output column), all tracked as integer
-// exponents and undone exactly with ldexp.  NaN / Inf propagate (a non-finite maximum leaves the scale at 1).
+// exponents (clamped to +-110) and undone exactly with ldexp.
+//
+// Non-finite values: a NaN or Inf in a point's input row, in its dY row or in a weight reaches every output that depends on it
+// as a non-finite value (tests/test_gpu_mlp_range.py) and leaves the other points' results bit-identical.  The maxima skip a NaN
+// (fmaxf) and a non-finite maximum leaves the scale at 1, so the value itself goes through the f16 conversion; the ReLU keeps a NaN
+// (relu() below); an Inf operand has lo = Inf - Inf = NaN, so what comes out may be NaN where exact arithmetic gives Inf, and a
+// non-finite weight makes its whole matrix unscaled.  The backward masks with h > 0: a NaN activation passes no gradient.
+//
+// Range (same tests, against float64 with the bound tests/mlp_ref.py derives from this format): the lo part is an f16 too, so an
+// operand is carried to max(2^-22 |v|, 2^-25 / scale), i.e. to 2^-38 of ITS GROUP'S maximum -- not of its own magnitude.  A weight
+// row 2^-30 below its matrix's maximum, or an input column 2^-30 below its row's, keeps 8 bits.  Outputs stay inside the bound
+// (it is absolute), but a result carried by such operands alone is only that good.
 #pragma once
 #include "common.hpp"
 #include "split_rows.hpp"
@@ -49,6 +60,10 @@ __device__ __forceinline__ f32x16 zero16() {
 }
 
 __device__ __forceinline__ float pow2f(int k) { return ldexpf(1.0f, k); }
+
+// ReLU that keeps a NaN: IEEE 754-2019 maximum (gfx950's v_maximum3_f32, one instruction), where fmaxf / v_max_f32 (IEEE maxNum)
+// returns 0 for a NaN.  A NaN in one input column makes every hidden pre-activation of the point NaN, and it must stay one.
+__device__ __forceinline__ float relu(float a) { return __builtin_elementwise_maximum(a, 0.f); }
 
 // Cross-lane maxima without the LDS crossbar.  __shfl_xor compiles to ds_bpermute_b32 (address arithmetic, an LDS-queue
 // instruction, s_waitcnt lgkmcnt(0)): a wave that is alone on its SIMD pays ~100 cycles for each, and the per-tile row maximum
@@ -1189,7 +1204,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsi
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) a0[t][r] = fmaxf(a0[t][r], 0.f);
+      for (int r = 0; r < 16; ++r) a0[t][r] = relu(a0[t][r]);
     if (a.h_save) {                                // kept for callers that want the hidden activations
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -1207,7 +1222,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsi
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) a1[t][r] = fmaxf(a1[t][r], 0.f);
+        for (int r = 0; r < 16; ++r) a1[t][r] = relu(a1[t][r]);
       if (a.h_save) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {

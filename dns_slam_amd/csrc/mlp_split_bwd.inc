@@ -300,7 +300,7 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) h1[t][r] = fmaxf(h1[t][r], 0.f);
+      for (int r = 0; r < 16; ++r) h1[t][r] = relu(h1[t][r]);
     if constexpr (NL == 2) {
       const int kf = scale_exp(tile_max<NT>(h1));
       layer_chain<PREC, NT, NT>(h1, pow2f(kf), img_h, lane, h2);
@@ -308,7 +308,7 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) h2[t][r] = fmaxf(h2[t][r], 0.f);
+        for (int r = 0; r < 16; ++r) h2[t][r] = relu(h2[t][r]);
     }
     }
     f32x16(&hl)[NT] = (NL == 2) ? h2 : h1;
