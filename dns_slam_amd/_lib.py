@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class DnsGridMeta(C.Structure):
@@ -156,6 +156,10 @@ SIGNATURES = {
     "dns_tsdf_vertex_emit": (C.c_int, [_P, _U, _P, _P, C.c_double, _P, _P, C.c_uint64, _P]),
     "dns_convex_hull_ws_bytes": (C.c_uint64, [_U, _U]),
     "dns_convex_hull": (C.c_int, [_P, _U, C.c_double, _P, _U, _P, _P, C.POINTER(_U), C.POINTER(C.c_double), _P]),
+    "dns_stem_partial_rows": (C.c_uint64, [_U, _U, _U]),
+    "dns_stem_forward": (C.c_int, [_P, _U, _U, _U, _P, _P, _P, _U, _P, _P]),
+    "dns_stem_batch_stats": (C.c_int, [_P, _U, _U, _U, _P, _P, C.c_double, _P, _P, _P]),
+    "dns_stem_normalise": (C.c_int, [_P, C.c_uint64, _P, _P]),
 }
 
 

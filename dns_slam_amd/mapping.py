@@ -969,7 +969,11 @@ class Mapper:
         label, gt_c2w, cur_c2w) -> (cur_c2w [4,4], fine_loss_dict)`` with keys loss_camera_tensor, p_loss, d_loss,
         l_loss, lt_loss, smooth_loss; refined keyframe poses are written back into ``self.keyframe_dict`` (:914-926).
         The frame bundles come from ``set_target_refer_frames``; the frozen image stem ``self.encoder`` (:846) runs once
-        per call when set (else the 2-D code is zero).  ``optimize(n_iters, idx, target_frames_dict)`` -- the bundle given
+        per call when set (else the 2-D code is zero).  The encoder's ``bn=`` decides which codes the map is trained on:
+        ``encoder.ResNet(bn="batch")`` normalises with the statistics of this call's n_target * n_refer images, as the reference
+        does (it never puts its stem in eval() mode); the default "frozen" uses the running statistics.  A ``backend="hip"``
+        encoder returns channels-last storage, which ``.clone()`` keeps, so no re-layout copy is made downstream.
+        ``optimize(n_iters, idx, target_frames_dict)`` -- the bundle given
         directly -- is accepted too and is what ``optimize_frames`` takes."""
         if isinstance(cur_gt_color, dict):
             return self.optimize_frames(n_iters, cur_idx, cur_gt_color, **kw)

@@ -177,13 +177,21 @@ class Mesher:
     def keyframe_stem(self, keyframe_dict, encoder=None, batch=4):
         """The stem maps of the keyframes' ``gt_color`` (``encoder`` or ``mapper.encoder``, ``batch`` keyframes per call) as
         the channels-last fp32 stack [K, h, w, 64] that ``ops.keyframe_codes`` reads.  The stack stays on the device for the
-        whole extraction: K * 64 * h * w * 4 bytes, 52 MB per keyframe at Replica resolution (h x w = 340 x 600)."""
+        whole extraction: K * 64 * h * w * 4 bytes, 52 MB per keyframe at Replica resolution (h x w = 340 x 600).
+        An ``encoder.ResNet(backend="hip")`` writes each batch straight into its slice of the stack.  The encoder's ``bn=`` decides
+        the codes: "frozen" normalises with the running statistics; "batch" -- what the reference computes, and what a map it
+        trained expects -- with the statistics of each call's own images, so there the maps depend on ``batch``."""
         enc = encoder if encoder is not None else getattr(self.mapper, "encoder", None)
         if enc is None:
             raise ValueError("Mesher.keyframe_stem: no encoder (mapper.encoder is None and encoder= was not given)")
         out = None
         for s in range(0, len(keyframe_dict), batch):
             img = torch.stack([torch.as_tensor(kf["gt_color"]).to(self.device).float() for kf in keyframe_dict[s:s + batch]])
+            if getattr(enc, "backend", "torch") == "hip":
+                if out is None:
+                    out = torch.empty(len(keyframe_dict), *ops.stem_out_shape(img.shape[1], img.shape[2]), 64, device=self.device)
+                enc.forward_channels_last(img, out=out[s:s + img.shape[0]])
+                continue
             f = enc(img[None])[0].float()                                    # [n, C, h, w]
             if out is None:
                 out = torch.empty(len(keyframe_dict), f.shape[2], f.shape[3], f.shape[1], device=self.device)

@@ -1773,3 +1773,107 @@ def convex_hull(points: torch.Tensor, eps: float = 0.0):
     per inserted point: it cannot be captured into a graph (csrc/hull_topology.hpp)."""
     faces, planes, info = convex_hull_launch(points, eps)
     return torch.unique(faces.reshape(-1)), faces, planes, info["max_outside"]
+
+
+# ----------------------------------------------------------------------------- image stem (csrc/stem.hip)
+STEM_STATS, STEM_EPILOGUE, STEM_STORE = 1, 2, 4          # include/dns_hip.h: flags of dns_stem_forward
+_STEM_CACHE = {}
+
+
+def _stem_constants(conv_weight, bn_weight, bn_bias, running_mean, running_var, eps):
+    """The packed [148][64] weight image and the frozen-mode (s, t) [2][64], computed in float64 from the parameters (torch ops on
+    the device, no read-back) and cached per parameter version (address and ``_version``: a write through ``.data`` is not seen).
+    An entry holds its parameters, so that no other tensor can take their addresses while it lives."""
+    params = (conv_weight, bn_weight, bn_bias, running_mean, running_var)
+    key = tuple((t.data_ptr(), t._version) for t in params) + (float(eps),)
+    hit = _STEM_CACHE.get(key)
+    if hit is not None:
+        return hit[0], hit[1]
+    wpack = torch.zeros(148, 64, device=conv_weight.device)
+    wpack[:147] = conv_weight.detach().permute(2, 3, 1, 0).reshape(147, 64)             # row (ky 7 + kx) 3 + c, column o
+    s = bn_weight.detach().double() / torch.sqrt(running_var.detach().double() + float(eps))
+    t = bn_bias.detach().double() - running_mean.detach().double() * s
+    st = torch.stack((s, t)).float().contiguous()
+    if len(_STEM_CACHE) >= 8:
+        _STEM_CACHE.clear()
+    _STEM_CACHE[key] = (wpack, st, params)
+    return wpack, st
+
+
+def stem_out_shape(H: int, W: int):
+    """(h, w) of the stem maps of H x W images: conv 7x7, stride 2, padding 3."""
+    return (int(H) - 1) // 2 + 1, (int(W) - 1) // 2 + 1
+
+
+def stem_forward(images: torch.Tensor, conv_weight: torch.Tensor, bn_weight: torch.Tensor, bn_bias: torch.Tensor,
+                 running_mean: torch.Tensor, running_var: torch.Tensor, eps: float = 1e-5, *, batch_stats: bool = False,
+                 out: Optional[torch.Tensor] = None, batch_apply: str = "inplace") -> torch.Tensor:
+    """The image stem (reference models/layers.py:56-58,95-98): conv 7x7 stride 2 pad 3 (``conv_weight`` [64,3,7,7], exact fp32) +
+    batch-norm + ReLU of channels-last ``images`` [n,H,W,3] -> channels-last maps [n,h,w,64], h = (H-1)//2 + 1, w = (W-1)//2 + 1:
+    the layout ``feature_gather`` and ``keyframe_codes`` read, written once.
+
+    ``batch_stats=False``: the frozen statistics, nn.BatchNorm2d in eval() mode -- y = relu(conv s + t) with
+    s = weight / sqrt(running_var + eps), t = bias - running_mean s.  The bits of an image's map depend on the image alone.
+    ``batch_stats=True``: nn.BatchNorm2d in TRAIN mode, which is what the reference's never-eval()-ed stem computes: mean and biased
+    variance over the n h w values of each channel of THIS call (float64 sums of the fp32 conv values, added in a fixed order: the
+    same bits for every call); the running statistics are neither read nor updated.  ``batch_apply``: 'inplace' stores the raw
+    convolution and normalises it in place, 'recompute' runs the convolution a second time; both give the same bits.
+
+    ``out``: a contiguous [n,h,w,64] fp32 tensor, e.g. a slice of a [K,h,w,64] stack, written in place and returned.  No host
+    read-back; ValueError for a wrong dtype, device, rank, channel count or shape, for non-contiguous ``images`` / ``out``, and for
+    batch statistics of a single value (n h w = 1), which torch refuses too."""
+    params = (conv_weight, bn_weight, bn_bias, running_mean, running_var)
+    for t in (images,) + params + ((out,) if out is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("stem_forward: every tensor must be on the GPU (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"stem_forward: every tensor must be float32, got {t.dtype}")
+        if t.device != images.device:
+            raise ValueError("stem_forward: all tensors must be on one device")
+    if images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError(f"stem_forward: images must be channels-last [n,H,W,3], got {tuple(images.shape)}")
+    if not images.is_contiguous():
+        raise ValueError("stem_forward: images must be contiguous")
+    if tuple(conv_weight.shape) != (64, 3, 7, 7):
+        raise ValueError(f"stem_forward: conv_weight must be [64,3,7,7], got {tuple(conv_weight.shape)}")
+    for name, t in (("bn_weight", bn_weight), ("bn_bias", bn_bias), ("running_mean", running_mean), ("running_var", running_var)):
+        if tuple(t.shape) != (64,) or not t.is_contiguous():
+            raise ValueError(f"stem_forward: {name} must be a contiguous [64] tensor, got {tuple(t.shape)}")
+    if batch_apply not in ("inplace", "recompute"):
+        raise ValueError(f"stem_forward: batch_apply must be 'inplace' or 'recompute', got {batch_apply!r}")
+    n, H, W = (int(v) for v in images.shape[:3])
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError(f"stem_forward: images is empty {tuple(images.shape)}")
+    h, w = stem_out_shape(H, W)
+    if batch_stats and n * h * w == 1:
+        raise ValueError("stem_forward: batch statistics need more than one value per channel (n h w = 1)")
+    rows = int(_rawlib.dns_stem_partial_rows(n, H, W))
+    if rows == 0:
+        raise ValueError(f"stem_forward: images {tuple(images.shape)} are too large for one call")
+    if out is None:
+        out = torch.empty(n, h, w, 64, device=images.device)
+    elif tuple(out.shape) != (n, h, w, 64):
+        raise ValueError(f"stem_forward: out must be [{n},{h},{w},64], got {tuple(out.shape)}")
+    elif not out.is_contiguous():
+        raise ValueError("stem_forward: out must be contiguous")
+    wpack, st = _stem_constants(*params, eps)
+    images = images.detach()
+    sp = stream_ptr()
+    if not batch_stats:
+        check(lib.dns_stem_forward(ptr(images), n, H, W, ptr(wpack), ptr(st), ptr(out), STEM_STORE | STEM_EPILOGUE, None, sp),
+              "dns_stem_forward")
+        return out
+    ws = torch.empty((rows + 256) * 128, dtype=torch.float64, device=images.device)
+    level1 = ws[rows * 128:]
+    st_b = torch.empty(2, 64, device=images.device)
+    inplace = batch_apply == "inplace"
+    check(lib.dns_stem_forward(ptr(images), n, H, W, ptr(wpack), None, ptr(out), STEM_STATS | (STEM_STORE if inplace else 0), ptr(ws),
+                               sp), "dns_stem_forward")
+    check(lib.dns_stem_batch_stats(ptr(ws), n, H, W, ptr(bn_weight.detach()), ptr(bn_bias.detach()), float(eps), ptr(level1), ptr(st_b),
+                                   sp), "dns_stem_batch_stats")
+    if inplace:
+        check(lib.dns_stem_normalise(ptr(out), n * h * w, ptr(st_b), sp), "dns_stem_normalise")
+    else:
+        check(lib.dns_stem_forward(ptr(images), n, H, W, ptr(wpack), ptr(st_b), ptr(out), STEM_STORE | STEM_EPILOGUE, None, sp),
+              "dns_stem_forward")
+    return out

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 21
+#define DNS_ABI_VERSION 22
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -891,6 +891,31 @@ int dns_tsdf_vertex_emit(const int32_t* units, uint32_t B, const float* tsdf, co
 uint64_t dns_convex_hull_ws_bytes(uint32_t N, uint32_t face_cap);
 int dns_convex_hull(const double* points, uint32_t N, double eps, void* ws, uint32_t face_cap, int32_t* faces_out,
                     double* planes_out, uint32_t* n_faces_out, double* info, void* stream);
+
+/* ---- image stem (reference models/layers.py:56-58,95-98 through models/encoder.py:9-17; csrc/stem.hip, csrc/stem_tile.hpp; ABI v22)
+ * conv 7x7 stride 2 zero-pad 3, 3 -> 64 channels, no bias, exact fp32 products and fp32 accumulation in (ky, kx, c) order; then
+ * y = relu(fma(conv, s_c, t_c)), the ReLU keeping a NaN.  images [n,H,W,3] fp32 channels-last; out [n,h,w,64] fp32 channels-last,
+ * h = (H-1)/2 + 1, w = (W-1)/2 + 1, 128-byte aligned.  wpack [148][64]: weight[o][c][ky][kx] at row (ky 7 + kx) 3 + c, column o,
+ * row 147 zero; 16-byte aligned.  st [2][64]: s then t.  The bits of an image's map depend on nothing but the image, wpack and st.
+ * flags of dns_stem_forward:
+ *   DNS_STEM_STORE | DNS_STEM_EPILOGUE  the normalised maps (frozen statistics: st from the running statistics);
+ *   DNS_STEM_STATS [| DNS_STEM_STORE]   one row [2][64] float64 per workgroup in `partials` -- sums of conv and conv^2 over the
+ *                                       workgroup's pixels, taken from the fp32 conv values -- dns_stem_partial_rows(n, H, W)
+ *                                       rows (0 = shape refused); with DNS_STEM_STORE the raw convolution is stored as well.
+ * Any other combination is refused.
+ * dns_stem_batch_stats adds the rows in a fixed order (level1: scratch of 256 rows) and writes st for nn.BatchNorm2d's TRAIN
+ * mode: mean and biased variance over the n h w values of a channel, s = gamma / sqrt(var + eps), t = beta - mean s in float64,
+ * rounded to fp32; n h w = 1 is refused.  Running statistics are neither read nor written.  dns_stem_normalise applies
+ * y = relu(fma(y, s_c, t_c)) in place to [n_pixels][64] raw values: the bits DNS_STEM_EPILOGUE stores.  No atomics anywhere. */
+#define DNS_STEM_STATS 1u
+#define DNS_STEM_EPILOGUE 2u
+#define DNS_STEM_STORE 4u
+uint64_t dns_stem_partial_rows(uint32_t n, uint32_t H, uint32_t W);
+int dns_stem_forward(const float* images, uint32_t n, uint32_t H, uint32_t W, const float* wpack, const float* st, float* out,
+                     uint32_t flags, double* partials, void* stream);
+int dns_stem_batch_stats(const double* partials, uint32_t n, uint32_t H, uint32_t W, const float* gamma, const float* beta,
+                         double eps, double* level1, float* st, void* stream);
+int dns_stem_normalise(float* out, uint64_t n_pixels, const float* st, void* stream);
 
 #ifdef __cplusplus
 }
