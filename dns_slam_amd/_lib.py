@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class DnsGridMeta(C.Structure):
@@ -160,6 +160,9 @@ SIGNATURES = {
     "dns_stem_forward": (C.c_int, [_P, _U, _U, _U, _P, _P, _P, _U, _P, _P]),
     "dns_stem_batch_stats": (C.c_int, [_P, _U, _U, _U, _P, _P, C.c_double, _P, _P, _P]),
     "dns_stem_normalise": (C.c_int, [_P, C.c_uint64, _P, _P]),
+    "dns_frame_codes_ws_floats": (C.c_uint64, [_U, _U, _U, _U, _U, _U, _U, _U]),
+    "dns_frame_codes": (C.c_int, [_P, _U, _P, _P, _U, C.POINTER(C.c_float), _P, _U, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _U, _P,
+                                  _U, _U, _U, _P, C.c_uint64, _P, _U, _U, _P]),
 }
 
 

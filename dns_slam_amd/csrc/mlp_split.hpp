@@ -1084,9 +1084,10 @@ struct FwdArgs {
 
 // XS: the input arrives in the split-row format (split_rows.hpp) and goes from memory straight into the B operand
 // (a __device__ body so that the fused tracker iteration, track_fused.inc, can run it as one of its phases: vb = the workgroup's
-//  index in this launch's grid, lds = the workgroup's dynamic LDS)
+//  index in this launch's grid, lds = the workgroup's dynamic LDS; images_ready: the caller has built weight set 0's images in
+//  this LDS already (build_fwd_images + a barrier) and calls the body many times on them -- frame_codes.hip, once per tile)
 template <int NN, int NL, int PREC, bool XS = false>
-__device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsigned char* lds) {
+__device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsigned char* lds, bool images_ready = false) {
   constexpr int NT = NN / 32;
   using L = FwdLds<NN, NL>;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -1105,7 +1106,7 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsi
   XChunk xc[XS ? 1 : 4];                         // n_in <= 128: at most 4 chunks of 32 columns
   XsTile xt;                                     // (XS) the tile's operand fragments
   uint32_t cur_buf = 1;
-  int cur_group = -2;
+  int cur_group = images_ready ? 0 : -2;
   const rsrc_t r_y = buf_make(a.y), r_hs = buf_make(a.h_save);
   uint32_t* yoff = reinterpret_cast<uint32_t*>(stg + STG_WAVE_FLOATS);      // byte offsets of the tile's rows in y (BUF_OOB: padding)
   const uint32_t y_row_limit = BUF_LIMIT / (4u * max(a.ldy, 1u));

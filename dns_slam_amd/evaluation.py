@@ -326,12 +326,16 @@ def semantic_metrics(conf, n_invalid=None) -> dict:
             "total_accuracy": float(diag.sum() / total), "iou": iou}
 
 
-def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_batch=None, jitters=None) -> dict:
+def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_batch=None, jitters=None, stem=None, truncate=False,
+                   code_method=None) -> dict:
     """The loop of eval_2d.py:398-411: for each chosen frame i (``indices``, or every ``every``-th frame) ``mapper.render_frame``
     from ``frames["est_c2w"][i]``, then PSNR over the pixels with gt_depth > 0, MS-SSIM and the four semantic figures of the
     arg-max label image against ``frames["gt_label"][i]`` (classes = the decoder's n_class).  The metric kernels are queued behind
     each render; the host reads everything back once, after the last frame.  ``features`` / ``jitters``: per chosen frame, what
-    ``render_frame`` takes (None: no 2-D code / fresh draws).  -> {"frames": [i...], "psnr", "ssim", "miou", "fwiou",
+    ``render_frame`` takes (None: no 2-D code / fresh draws).  ``stem``: the 2-D code from reference views, computed chunk by
+    chunk (``render_frame(refer_frames=...)``; exclusive with ``features``) -- "self" = the frame itself at its estimated pose as
+    the single view, what novel_view_render renders with (eval_2d.py:239-240), or a callable i -> refer_frames for anything else;
+    ``truncate`` / ``code_method`` are passed through.  -> {"frames": [i...], "psnr", "ssim", "miou", "fwiou",
     "class_avg_accuracy", "total_accuracy": {"per_frame": float64 array, "mean": float}}; no "lpips" (see the module docstring)."""
     n = int(frames["gt_color"].shape[0])
     idx = list(range(0, n, int(every))) if indices is None else [int(i) for i in indices]
@@ -340,14 +344,24 @@ def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_
     for name, seq in (("features", features), ("jitters", jitters)):
         if seq is not None and len(seq) != len(idx):
             raise ValueError(f"render_metrics: {name} must hold one entry per chosen frame ({len(idx)}), got {len(seq)}")
+    if stem is not None and features is not None:
+        raise ValueError("render_metrics: stem= and features= are exclusive")
+    if stem is not None and stem != "self" and not callable(stem):
+        raise ValueError(f"render_metrics: stem must be None, 'self' or a callable i -> refer_frames, got {stem!r}")
     dev = mapper.device
     n_class = int(mapper.decoder.n_class)
     vals, mses, confs, bads = [], [], [], []
     for k, i in enumerate(idx):
         gt_color, gt_depth, gt_label = frames["gt_color"][i], frames["gt_depth"][i], frames["gt_label"][i]
+        refer = None
+        if stem == "self":
+            refer = {"gt_color": gt_color[None], "est_c2w": frames["est_c2w"][i][None]}
+        elif stem is not None:
+            refer = stem(i)
         color, _, label = mapper.render_frame(gt_color, gt_depth, gt_label, frames["est_c2w"][i],
                                               features=None if features is None else features[k], n_pts_batch=n_pts_batch,
-                                              jitter=None if jitters is None else jitters[k])
+                                              jitter=None if jitters is None else jitters[k], refer_frames=refer,
+                                              truncate=truncate, code_method=code_method)
         v, m, _, _ = ops.ms_ssim_launch(color, gt_color.to(dev), gt_depth.to(dev))
         cf, bad = ops.label_confusion(gt_label.to(dev).reshape(label.shape), label, n_class)
         vals.append(v), mses.append(m), confs.append(cf.reshape(-1)), bads.append(bad.reshape(1))

@@ -738,12 +738,25 @@ class Mapper:
 
     # ------------------------------------------------------------------ slams/mapping.py:638-724 (without the plotting)
     @torch.no_grad()
-    def render_frame(self, cur_gt_color, cur_gt_depth, cur_gt_label, cur_c2w, features=None, n_pts_batch=None, jitter=None):
+    def render_frame(self, cur_gt_color, cur_gt_depth, cur_gt_label, cur_c2w, features=None, n_pts_batch=None, jitter=None,
+                     refer_frames=None, truncate=False, code_method=None):
         """Full-image re-rendering of ``frame_vis``: all H*W rays of the frame (get_all_rays :540, box clip, ONE
         sample_along_rays over the whole image :661), then the renderer in chunks of ``n_pts_batch`` rays (:675-694;
         the reference's 1000 by default -- NB the tiled label layout (D1) makes the result depend on the chunk size).
-        Returns (pred_color [H,W,3], pred_depth [H,W], pred_label [H,W] = argmax of the composited logits)."""
+        Returns (pred_color [H,W,3], pred_depth [H,W], pred_label [H,W] = argmax of the composited logits).
+
+        The 2-D code: ``features`` [H*W, S, hid] is a finished tensor (4.9 GB at Replica size).  ``refer_frames`` instead names
+        the reference views -- {"gt_color": [R,H,W,3], "est_c2w": [R,4,4]}, or "stem": [R,h,w,Cs] channels-last maps in place of
+        "gt_color" -- and every chunk's code is computed inside the chunk loop by ``ops.frame_codes`` (``code_method``: its
+        ``method``), as the reference does it (:666-689): the extra memory is one chunk's code.  With "gt_color" ``self.encoder``
+        runs once per frame on [1,R,H,W,3] (its ``bn=`` decides the statistics; a ``backend="hip"`` encoder writes the
+        channels-last maps directly); w2c = inverse(est_c2w).  Giving both ``features`` and ``refer_frames`` is an error.
+        ``truncate``: the reference TRAINS with the code masked to the samples near the measured depth (:553-557) and RENDERS
+        without the mask (frame_vis does not mask).  False (default) is what the reference renders with; True applies the
+        training-time mask with the frame's ``gt_depth`` (as ``keep``), i.e. the code the map was trained on."""
         H, W = self.H, self.W
+        if features is not None and refer_frames is not None:
+            raise ValueError("render_frame: features= and refer_frames= are exclusive")
         n_pts_batch = n_pts_batch or self.cfg["mapping"].get("n_pts_batch", 1000)
         dev = self.device
         quat = get_quad_from_c2w(cur_c2w).to(dev)[None]
@@ -756,10 +769,21 @@ class Mapper:
             quat, trans, pix, f(cur_gt_color), f(cur_gt_depth), f(cur_gt_label), (self.fx, self.fy, self.cx, self.cy),
             self.bound, (0, H, 0, W), H * W, self.t_uniform, jitter[0], jitter[1])
         S = z.shape[1]
+        if refer_frames is not None:
+            stem, w2c = self.refer_stem(refer_frames)
+            origins = torch.inverse(w2c)[:, :3, 3].contiguous()            # refer_o of feature_matching: once per frame
+            keep = None
+            if truncate:
+                d = gt_depth[:, None]
+                keep = (~(z < d * 0.95) & ~(z > d * 1.05) & (d > 0.0)).reshape(-1)       # :553-556 as a mask
         colors, depths, labels = [], [], []
         for start in range(0, H * W, n_pts_batch):
             end = min(start + n_pts_batch, H * W)
-            if features is None:
+            if refer_frames is not None:
+                code = ops.frame_codes(pts[start:end].reshape(-1, 3), w2c, stem, (self.fx, self.fy, self.cx, self.cy), H, W,
+                                       self.decoder.merge, keep=None if keep is None else keep[start * S:end * S],
+                                       method=code_method, origins=origins).reshape(end - start, S, -1)
+            elif features is None:
                 # no 2-D code: a code of ZERO columns -- the colour / logit networks run as their live (OneBlob + latent)-input
                 # networks (the reference multiplies a zero code through, :553-557; round 4 read a 537 MB block of zeros per chunk)
                 code = torch.empty(end - start, S, 0, device=dev)
@@ -770,6 +794,44 @@ class Mapper:
             color, depth, _, logits, _, _ = self.renderer(samples, strict=False, need_coarse=False)
             colors.append(color), depths.append(depth), labels.append(torch.argmax(logits, dim=-1))
         return torch.cat(colors).reshape(H, W, 3), torch.cat(depths).reshape(H, W), torch.cat(labels).reshape(H, W)
+
+    @torch.no_grad()
+    def refer_stem(self, refer_frames):
+        """``refer_frames`` of ``render_frame`` -> (stem maps [R,h,w,Cs] fp32 channels-last, w2c [R,4,4])."""
+        dev = self.device
+        c2w = torch.as_tensor(refer_frames["est_c2w"]).to(dev).float()
+        if c2w.dim() != 3 or c2w.shape[1:] != (4, 4):
+            raise ValueError(f"render_frame: refer_frames['est_c2w'] must be [R,4,4], got {tuple(c2w.shape)}")
+        if "stem" in refer_frames:
+            if "gt_color" in refer_frames:
+                raise ValueError("render_frame: refer_frames holds 'gt_color' or 'stem', not both")
+            stem = refer_frames["stem"].to(dev).float().contiguous()
+        else:
+            enc = getattr(self, "encoder", None)
+            if enc is None:
+                raise ValueError("render_frame: refer_frames['gt_color'] needs the mapper's encoder (Mapper.encoder)")
+            images = refer_frames["gt_color"].to(dev).float()                             # [R,H,W,3]: one batch of the stem
+            if hasattr(enc, "forward_channels_last") and getattr(enc, "backend", None) == "hip":
+                stem = enc.forward_channels_last(images)                                 # no re-layout copy
+            else:
+                stem = enc(images[None])[0].permute(0, 2, 3, 1).contiguous().float()     # [R,C,h,w] -> channels last
+        if stem.dim() != 4 or stem.shape[0] != c2w.shape[0]:
+            raise ValueError(f"render_frame: {tuple(stem.shape)} stem maps for {c2w.shape[0]} poses")
+        return stem, torch.inverse(c2w)
+
+    def vis_refer_frames(self, cur_gt_color, cur_c2w):
+        """The reference views ``frame_vis`` renders with (:645-646, 663, 670): the bundle ``set_target_refer_frames`` builds for
+        the current frame -- the two latest keyframes, indices [max(last - 1, 0), max(last, 0)] with last = len(keyframe_list) - 1,
+        and the frame itself at ``cur_c2w`` -- as ``render_frame(refer_frames=...)`` takes it, plus "kf_idx" (-1 = the frame).
+        The reference gets there through ``set_target_refer_frames``, which draws random keyframes for the OTHER targets on
+        the way; this draws no random numbers.  Without any keyframe (where the reference's indexing fails) the frame is its own
+        single view."""
+        dev = self.device
+        kfs, last = self.keyframe_dict, len(self.keyframe_list) - 1
+        pair = [max(last - 1, 0), max(last, 0)] if last >= 0 else []
+        color = [kfs[r]["gt_color"].to(dev).float() for r in pair] + [cur_gt_color.to(dev).float()]
+        c2w = [kfs[r]["est_c2w"].to(dev).float() for r in pair] + [cur_c2w.to(dev).float()]
+        return {"gt_color": torch.stack(color, 0), "est_c2w": torch.stack(c2w, 0), "kf_idx": pair + [-1]}
 
     # ------------------------------------------------------------------ slams/mapping.py:887-907
     def iteration_loss(self, samples, lambda_lt=10.0, smooth=True, u_offset=None, u_jitter=None, strict=False):

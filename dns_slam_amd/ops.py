@@ -1176,6 +1176,127 @@ def keyframe_codes(points: torch.Tensor, w2c: torch.Tensor, origins: torch.Tenso
     return code, count
 
 
+# ----------------------------------------------------------------------------- frame codes (csrc/frame_codes.hip)
+FRAME_CODES_METHODS = ("fused", "launches")
+
+
+FRAME_CODES_DEFAULT = "fused"              # what ``method=None`` means where the fused kernel takes the shape
+
+
+def frame_codes_fused_ok(merge, Cs: int) -> bool:
+    """The shapes ``frame_codes(method="fused")`` takes (the ones ``launch.Stem2D`` accepts, on the fp32-grade kernels):
+    n_in = 3 n_bins + Cs with both parts multiples of 4 (and n_in one of 8, at most 128), hid a multiple of 4 up to 64, a Merge
+    network of 32 x 1 or 64 x 2 that is not ``fp16``."""
+    net = merge.decoder
+    n_pe, hid = 3 * int(merge.pe_fn.n_bins), int(net.n_output_dims)
+    n_in = n_pe + int(Cs)
+    return (n_in == int(net.n_input_dims) and n_pe % 4 == 0 and n_pe > 0 and Cs % 4 == 0 and Cs > 0 and n_in % 8 == 0
+            and n_in <= 128 and hid % 4 == 0 and 0 < hid <= 64 and not getattr(net, "fp16", False)
+            and (int(net.n_neurons), int(net.n_hidden_layers)) in ((32, 1), (64, 2)))
+
+
+@torch.no_grad()
+def frame_codes(pts: torch.Tensor, refer_w2c: torch.Tensor, stem_nhwc: torch.Tensor, cam, H: int, W: int, merge, *, keep=None,
+                method: Optional[str] = None, out: Optional[torch.Tensor] = None, tile: int = 0,
+                origins: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 2-D code of the points of a rendered frame: pts [P,3] world, refer_w2c [R,4,4], stem_nhwc [R,h,w,Cs] fp32 (the stem
+    maps, channels last, half resolution), cam {'fx','fy','cx','cy'} (or the four values), ``merge`` the ``Decoder.merge`` module
+    -> code [P, hid] fp32: exactly ``common.feature_matching(H, W, K, pts, refer_w2c, maps, merge)`` -- per view the code at the
+    rounded projected pixel (zeros where the view does not see the point), Merge on OneBlob(p - o_r) + code, the mean over the views
+    (reference utils/common.py:645-679, models/decoder.py:67-77, as frame_vis and novel_view_render call them per chunk:
+    slams/mapping.py:666-689, eval_2d.py:260-283).  Forward only.
+
+    ``keep`` [P] uint8 / bool: a point with 0 gets a zero row and none of its taps are read.
+    ``method="fused"``: one kernel (csrc/frame_codes.hip); the Merge rows live in a workgroup-private workspace slice.  ``"launches"``: the composition of
+    the existing launches, ``common.feature_matching`` times ``keep`` -- the yardstick and the fallback.  A shape the fused kernel
+    does not take (``frame_codes_fused_ok``) raises.  ``method=None`` (the default) is ``FRAME_CODES_DEFAULT`` where the fused kernel
+    takes the shape and ``"launches"`` where it does not, without comment.
+    ``out``: a float32 [P, hid] tensor to write into (rows of a larger tensor are fine).  ``tile``: points a workgroup of the fused
+    kernel takes at a time, 32, 64 or 128 (0: chosen by the library from the point count; the bits do not depend on it).
+    ``origins`` [R,3]: ``torch.inverse(refer_w2c)[:, :3, 3]`` where the caller has it already (``render_frame`` computes it once
+    per frame, not once per chunk: the inverse reads its status back to the host); both methods take it."""
+    pts, w2c, R = _pose_args("frame_codes", pts, refer_w2c)
+    dev = pts.device
+    if method is not None and method not in FRAME_CODES_METHODS:
+        raise ValueError(f"frame_codes: method {method!r} (one of {FRAME_CODES_METHODS})")
+    if not (isinstance(stem_nhwc, torch.Tensor) and stem_nhwc.is_cuda and stem_nhwc.device == dev and stem_nhwc.dtype == torch.float32
+            and stem_nhwc.dim() == 4 and stem_nhwc.shape[0] == R):
+        raise ValueError(f"frame_codes: stem_nhwc must be a float32 [R,h,w,Cs] tensor on {dev} with R = {R}")
+    if R < 1:
+        raise ValueError("frame_codes: no reference view")
+    h, w_, Cs = (int(s) for s in stem_nhwc.shape[1:])
+    if h < 1 or w_ < 1 or Cs < 1 or H < 1 or W < 1:
+        raise ValueError(f"frame_codes: stem maps of {h} x {w_} x {Cs} for images of {H} x {W}")
+    net = merge.decoder
+    hid, n_bins = int(net.n_output_dims), int(merge.pe_fn.n_bins)
+    if net.params.device != dev:
+        raise ValueError(f"frame_codes: the Merge network lives on {net.params.device}, the points on {dev}")
+    if 3 * n_bins + Cs != int(net.n_input_dims):
+        raise ValueError(f"frame_codes: {3 * n_bins} encoding + {Cs} stem columns for a Merge network of {net.n_input_dims} inputs")
+    P = pts.shape[0]
+    if keep is not None:
+        if not (isinstance(keep, torch.Tensor) and keep.is_cuda and keep.device == dev and keep.dtype in (torch.uint8, torch.bool)
+                and keep.shape == (P,)):
+            raise ValueError(f"frame_codes: keep must be a uint8 or bool [P] = [{P}] tensor on {dev}")
+        keep = keep.detach().contiguous().view(torch.uint8)
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.float32
+                and out.shape == (P, hid)):
+            raise ValueError(f"frame_codes: out must be a float32 [P, hid] = [{P}, {hid}] tensor on {dev}")
+    fused_ok = frame_codes_fused_ok(merge, Cs)
+    if method is None:
+        method = FRAME_CODES_DEFAULT if fused_ok else "launches"
+    if method == "fused" and not fused_ok:
+        raise ValueError(f"frame_codes: method='fused' takes 3 n_bins and Cs multiples of 4 (their sum one of 8, at most 128), hid a "
+                         f"multiple of 4 up to 64 and an fp32-grade Merge network of 32 x 1 or 64 x 2; got n_bins {n_bins}, Cs {Cs}, "
+                         f"hid {hid}, {net.n_neurons} x {net.n_hidden_layers}{', fp16' if getattr(net, 'fp16', False) else ''}")
+    fx, fy, cx, cy = (cam["fx"], cam["fy"], cam["cx"], cam["cy"]) if isinstance(cam, dict) else cam
+    feat = stem_nhwc.detach().contiguous()
+    if origins is not None:
+        if not (isinstance(origins, torch.Tensor) and origins.is_cuda and origins.device == dev and origins.shape == (R, 3)
+                and origins.is_floating_point()):
+            raise ValueError(f"frame_codes: origins must be a floating-point [R,3] = [{R},3] tensor on {dev}")
+        origins = origins.detach().float().contiguous()
+    if method == "launches":
+        K = torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+        if P == 0:
+            code = torch.zeros(0, hid, device=dev)
+        elif origins is None:
+            from .common import feature_matching
+            code = feature_matching(H, W, K, pts, w2c, feat.permute(0, 3, 1, 2), merge)
+        else:
+            # feature_matching (common.py) with the origins handed over instead of inverted
+            gathered, _ = feature_gather(pts, w2c, K, feat, H, W)
+            code = merge(pts[None, :, :] - origins[:, None, :], origins, gathered)
+        if keep is not None:
+            code = code * keep[:, None].to(code.dtype)
+        if out is None:
+            return code
+        out.copy_(code)
+        return out
+    direct = out is not None and out.stride(1) == 1 and out.stride(0) % 4 == 0 and out.stride(0) >= hid and out.data_ptr() % 16 == 0
+    res = out if direct else torch.empty(P, hid, device=dev)
+    if P:
+        origin = torch.inverse(w2c)[:, :3, 3].contiguous() if origins is None else origins      # refer_o, as feature_matching takes it
+        params = net.params.detach()
+        if params.data_ptr() % 16 != 0 or not params.is_contiguous() or params.dtype != torch.float32:
+            params = params.float().contiguous().clone()
+        nn_, nl = int(net.n_neurons), int(net.n_hidden_layers)
+        n_ws = int(lib.dns_frame_codes_ws_floats(P, R, n_bins, Cs, hid, nn_, nl, int(tile)))
+        if n_ws == 0:
+            raise ValueError(f"frame_codes: {P} points x {R} views in tiles of {tile} refused (at most 64 views, fewer than 2^31 points, "
+                             f"tiles of 0 = automatic, 32, 64 or 128)")
+        ws = torch.empty(n_ws, device=dev)
+        K9 = (C.c_float * 9)(float(fx), 0.0, float(cx), 0.0, float(fy), float(cy), 0.0, 0.0, 1.0)
+        check(lib.dns_frame_codes(ptr(pts), P, ptr(w2c), ptr(origin), R, K9, ptr(feat), Cs, h, w_, H, W, ptr(keep),
+                                  _bound6(merge.bound), n_bins, ptr(params), nn_, nl, hid, ptr(ws), n_ws, ptr(res), res.stride(0),
+                                  int(tile), stream_ptr()), "dns_frame_codes")
+    if out is not None and not direct:
+        out.copy_(res)
+        return out
+    return res
+
+
 # ----------------------------------------------------------------------------- mesh components (csrc/mesh_cc.hip)
 def mesh_components(verts: torch.Tensor, faces: torch.Tensor):
     """verts [V,3] fp32, faces [F,3] int32 (any triangle list with shared vertex indices) -> (comp [F] int32: the smallest

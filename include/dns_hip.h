@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 22
+#define DNS_ABI_VERSION 23
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -916,6 +916,30 @@ int dns_stem_forward(const float* images, uint32_t n, uint32_t H, uint32_t W, co
 int dns_stem_batch_stats(const double* partials, uint32_t n, uint32_t H, uint32_t W, const float* gamma, const float* beta,
                          double eps, double* level1, float* st, void* stream);
 int dns_stem_normalise(float* out, uint64_t n_pixels, const float* st, void* stream);
+
+/* ---- the 2-D code of a frame's samples (csrc/frame_codes.hip, csrc/frame_codes_plan.hpp; ABI v23) -----------------------------
+ * Replaces, per chunk of a full-frame render, feature_matching (reference utils/common.py:645-679) + Decoder.merge
+ * (models/decoder.py:67-77) as frame_vis (slams/mapping.py:666-689) and novel_view_render (eval_2d.py:260-283) call them: one
+ * kernel, the Merge rows never reach HBM.  pts [P,3]; w2c [R,16] row-major world->camera; origin [R,3] = the translations of the
+ * inverse poses; K [host, 9 floats] row-major intrinsics; feat [R,h,w,C] fp32 channels-last stem maps; keep [P] bytes or NULL;
+ * bound [host, 6 doubles] b0x,b1x,b0y,b1y,b0z,b1z = Merge's bound; params = the Merge network's fp32 weights (3 n_bins + C inputs,
+ * hid outputs, n_neurons x n_hidden_layers = 32 x 1 or 64 x 2).  out [P][ld_out], columns [0, hid).
+ * Per view r: the projection and validity test of dns_feature_gather (y and z flipped, u = rint(q0 / (q2 + 1e-5)), valid iff
+ * 0 < u < W-1, 0 < v < H-1, cz > 0); the code is the bilinear value (align_corners=True) of the half-resolution map at that integer
+ * pixel -- dns_feature_gather's bits -- or zeros where the view is not valid (no tap is read then); the row is OneBlob of
+ * (p - origin_r), normalised with bound in fp64 (dns_encode_fwd's bits), followed by the code; the latent is the network on the row
+ * (dns_mlp_fwd's bits).  out = (latent_0 + latent_1 + ... in view order) / R.  keep[p] == 0: a zero row, none of p's taps read.
+ * No atomics: the same bits for every call, every split of the points and every tile_pts.  tile_pts = the points a workgroup
+ * takes at a time: 0 = chosen by the library (128, or 64 / 32 where the points would not fill the device), else 32, 64 or 128.
+ * ws: dns_frame_codes_ws_floats(...) floats for the same tile_pts, 16-byte aligned; 0 = shape refused (C or 3 n_bins no multiple of
+ * 4, 3 n_bins + C no multiple of 8 or above 128, hid no multiple of 4 or above 64, R above 64, another network shape or tile).
+ * feat, params and out 16-byte aligned, ld_out a multiple of 4.  P = 0: nothing is launched. */
+uint64_t dns_frame_codes_ws_floats(uint32_t P, uint32_t R, uint32_t n_bins, uint32_t C, uint32_t hid, uint32_t n_neurons,
+                                   uint32_t n_hidden_layers, uint32_t tile_pts);
+int dns_frame_codes(const float* pts, uint32_t P, const float* w2c, const float* origin, uint32_t R, const float* K,
+                    const float* feat, uint32_t C, int h, int w, int H, int W, const uint8_t* keep, const double* bound,
+                    uint32_t n_bins, const float* params, uint32_t n_neurons, uint32_t n_hidden_layers, uint32_t hid,
+                    float* ws, uint64_t ws_floats, float* out, uint32_t ld_out, uint32_t tile_pts, void* stream);
 
 #ifdef __cplusplus
 }
