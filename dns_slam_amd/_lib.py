@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class DnsGridMeta(C.Structure):
@@ -163,6 +163,12 @@ SIGNATURES = {
     "dns_frame_codes_ws_floats": (C.c_uint64, [_U, _U, _U, _U, _U, _U, _U, _U]),
     "dns_frame_codes": (C.c_int, [_P, _U, _P, _P, _U, C.POINTER(C.c_float), _P, _U, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _U, _P,
                                   _U, _U, _U, _P, C.c_uint64, _P, _U, _U, _P]),
+    "dns_conv_pack_shape": (C.c_int, [_U, _U, _U, _U, _U, C.POINTER(_U)]),
+    "dns_conv_cl": (C.c_int, [_P, _U, _U, _U, _U, _P, _P, _U, _U, _U, _U, _U, _P, _P]),
+    "dns_max_pool_cl": (C.c_int, [_P, _U, _U, _U, _U, _P, _P]),
+    "dns_lpips_head_blocks": (_U, [_U, _U]),
+    "dns_lpips_head": (C.c_int, [_P, _P, _P, _U, _U, _U, _U, _P, _P]),
+    "dns_lpips_finish": (C.c_int, [C.POINTER(_P), C.POINTER(_U), C.POINTER(_U), _U, _U, _P, _P, _P]),
 }
 
 

@@ -10,9 +10,14 @@ the alignment, then ``metrics_3d``.
 2-D evaluation and trajectory error: the reference's ``eval_2d.py`` and ``eval_ate.py``.  ``psnr`` / ``ms_ssim`` score rendered
 images (``ops.ms_ssim``: MS-SSIM and the masked MSE in one launch sequence), ``semantic_metrics`` turns a confusion matrix
 (``ops.label_confusion``) into mIoU / fwIoU / accuracies, ``render_metrics`` is the loop of eval_2d.py:398-411 over a frame list
-with one host read at the end, and ``evaluate_ate`` the absolute trajectory error after the closed-form rigid alignment.  LPIPS is
-not computed: it needs AlexNet and the LPIPS linear-layer weights, which this repository does not ship; the result dict has no
-``lpips`` key.
+with one host read at the end, and ``evaluate_ate`` the absolute trajectory error after the closed-form rigid alignment.
+
+LPIPS (eval_2d.py:81-82,304): ``lpips`` is ``ops.lpips``, the AlexNet tower and the distance head on the device, and
+``render_metrics(..., lpips=weights)`` queues it behind each frame's MS-SSIM.  The network weights are an input:
+``load_lpips_weights`` reads torchvision's AlexNet state dict and lpips v0.1's ``alex.pth`` from files the caller has; none is part
+of this repository and none is fetched.  Limit: neither the lpips package, torchvision nor a pretrained file was available where
+this was written, so the arithmetic is held to a float64 restatement of the published definition (include/dns_hip.h,
+tests/lpips_ref.py) with weights drawn from a seed, not to values the lpips package wrote.
 
 Depth L1: the reference's ``eval_3d.calc_2d_metric``.  ``view_box`` / ``look_at`` / ``sample_views`` draw the virtual cameras
 (``ops.views_see_any`` rejects those that see the unseen cloud), ``render_depth`` turns a mesh into depth images
@@ -299,6 +304,45 @@ def ms_ssim(pred, gt):
     return ops.ms_ssim(pred, gt)["ms_ssim"]
 
 
+LPIPS_FEATURE_KEYS = (0, 3, 6, 8, 10)             # torchvision AlexNet: features.{k}.weight / .bias of the five convolutions
+
+
+def _state_tensor(sd, key, shape, path):
+    if key not in sd:
+        raise ValueError(f"load_lpips_weights: {path}: key {key!r} is missing")
+    t = sd[key]
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"load_lpips_weights: {path}: key {key!r} holds a {type(t).__name__}, not a tensor")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"load_lpips_weights: {path}: key {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.detach().float()
+
+
+def load_lpips_weights(alexnet_path, lin_path) -> ops.LpipsWeights:
+    """The LPIPS parameters from two files the caller has: ``alexnet_path`` = torchvision's AlexNet state dict (keys
+    ``features.{0,3,6,8,10}.{weight,bias}``; other keys are ignored), ``lin_path`` = lpips v0.1's ``alex.pth`` (keys
+    ``lin{0..4}.model.1.weight``, each [1,C,1,1]); both read with ``torch.load(..., weights_only=True)``.  Every shape is checked;
+    a missing key, a wrong shape and a non-tensor entry raise ValueError naming the key.  -> ``ops.LpipsWeights`` (the device
+    copies and the packed weight images are made once per device, on first use).  No file is fetched."""
+    alex = torch.load(alexnet_path, map_location="cpu", weights_only=True)
+    lin = torch.load(lin_path, map_location="cpu", weights_only=True)
+    for sd, path in ((alex, alexnet_path), (lin, lin_path)):
+        if not isinstance(sd, dict):
+            raise ValueError(f"load_lpips_weights: {path} holds a {type(sd).__name__}, not a state dict")
+    convs, lins = [], []
+    for l, (k, cin, cout, ks, _, _, _) in enumerate(ops.LPIPS_LAYERS):
+        convs.append((_state_tensor(alex, f"features.{k}.weight", (cout, cin, ks, ks), alexnet_path),
+                      _state_tensor(alex, f"features.{k}.bias", (cout,), alexnet_path)))
+        lins.append(_state_tensor(lin, f"lin{l}.model.1.weight", (1, cout, 1, 1), lin_path).reshape(cout))
+    return ops.LpipsWeights(convs, lins)
+
+
+def lpips(pred, gt, weights, method=None):
+    """eval_2d.py:304: LearnedPerceptualImagePatchSimilarity(net_type='alex', normalize=True) per image pair, pred, gt [H,W,3] or
+    [F,H,W,3] in [0,1] (``ops.lpips``) -> float64 tensor (0-d or [F]) on the images' device."""
+    return ops.lpips(pred, gt, weights, method)["lpips"]
+
+
 def semantic_metrics(conf, n_invalid=None) -> dict:
     """eval_2d.py:180-213 from the confusion matrix conf [C,C] (rows = ground truth; ``ops.label_confusion``), on the host in
     float64 -> {"miou", "fwiou", "class_avg_accuracy", "total_accuracy", "iou" [C] (NaN for classes in neither image)}.  The
@@ -327,7 +371,7 @@ def semantic_metrics(conf, n_invalid=None) -> dict:
 
 
 def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_batch=None, jitters=None, stem=None, truncate=False,
-                   code_method=None) -> dict:
+                   code_method=None, lpips=None, lpips_method=None) -> dict:
     """The loop of eval_2d.py:398-411: for each chosen frame i (``indices``, or every ``every``-th frame) ``mapper.render_frame``
     from ``frames["est_c2w"][i]``, then PSNR over the pixels with gt_depth > 0, MS-SSIM and the four semantic figures of the
     arg-max label image against ``frames["gt_label"][i]`` (classes = the decoder's n_class).  The metric kernels are queued behind
@@ -336,7 +380,10 @@ def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_
     chunk (``render_frame(refer_frames=...)``; exclusive with ``features``) -- "self" = the frame itself at its estimated pose as
     the single view, what novel_view_render renders with (eval_2d.py:239-240), or a callable i -> refer_frames for anything else;
     ``truncate`` / ``code_method`` are passed through.  -> {"frames": [i...], "psnr", "ssim", "miou", "fwiou",
-    "class_avg_accuracy", "total_accuracy": {"per_frame": float64 array, "mean": float}}; no "lpips" (see the module docstring)."""
+    "class_avg_accuracy", "total_accuracy": {"per_frame": float64 array, "mean": float}}.  ``lpips``: an ``ops.LpipsWeights``
+    (``load_lpips_weights``): each frame's LPIPS is queued behind its MS-SSIM and the result gains "lpips": {"per_frame", "mean"},
+    still with the one host read (``lpips_method``: ``ops.lpips``'s ``method``); without it the launches and the result are what they
+    were, with no "lpips" key."""
     n = int(frames["gt_color"].shape[0])
     idx = list(range(0, n, int(every))) if indices is None else [int(i) for i in indices]
     if not idx:
@@ -348,9 +395,11 @@ def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_
         raise ValueError("render_metrics: stem= and features= are exclusive")
     if stem is not None and stem != "self" and not callable(stem):
         raise ValueError(f"render_metrics: stem must be None, 'self' or a callable i -> refer_frames, got {stem!r}")
+    if lpips is not None and not isinstance(lpips, ops.LpipsWeights):
+        raise ValueError("render_metrics: lpips must be None or the weights load_lpips_weights returns")
     dev = mapper.device
     n_class = int(mapper.decoder.n_class)
-    vals, mses, confs, bads = [], [], [], []
+    vals, mses, confs, bads, lps = [], [], [], [], []
     for k, i in enumerate(idx):
         gt_color, gt_depth, gt_label = frames["gt_color"][i], frames["gt_depth"][i], frames["gt_label"][i]
         refer = None
@@ -363,16 +412,20 @@ def render_metrics(mapper, frames, indices=None, every=10, features=None, n_pts_
                                               jitter=None if jitters is None else jitters[k], refer_frames=refer,
                                               truncate=truncate, code_method=code_method)
         v, m, _, _ = ops.ms_ssim_launch(color, gt_color.to(dev), gt_depth.to(dev))
+        if lpips is not None:
+            lps.append(ops.lpips_launch(color, gt_color.to(dev), lpips, lpips_method)[0])
         cf, bad = ops.label_confusion(gt_label.to(dev).reshape(label.shape), label, n_class)
         vals.append(v), mses.append(m), confs.append(cf.reshape(-1)), bads.append(bad.reshape(1))
-    host = torch.cat((torch.cat(vals), torch.cat(mses), torch.cat(bads).double(), torch.cat(confs).double())).cpu().numpy()
+    host = torch.cat((torch.cat(vals), torch.cat(mses), torch.cat(bads).double(), torch.cat(confs).double()) + tuple(lps)).cpu().numpy()
     F = len(idx)
     ssim, mse, bad = host[:F], host[F:2 * F], host[2 * F:3 * F]
-    conf = host[3 * F:].reshape(F, n_class, n_class)
+    conf = host[3 * F:3 * F + F * n_class * n_class].reshape(F, n_class, n_class)
     sem = [semantic_metrics(conf[k], bad[k]) for k in range(F)]
     per = {"psnr": -10.0 * np.log10(mse), "ssim": ssim.copy()}
     for key in ("miou", "fwiou", "class_avg_accuracy", "total_accuracy"):
         per[key] = np.array([s[key] for s in sem], np.float64)
+    if lpips is not None:
+        per["lpips"] = host[3 * F + F * n_class * n_class:].copy()
     out = {key: {"per_frame": v, "mean": float(np.mean(v))} for key, v in per.items()}
     out["frames"] = idx
     return out

@@ -1998,3 +1998,279 @@ def stem_forward(images: torch.Tensor, conv_weight: torch.Tensor, bn_weight: tor
         check(lib.dns_stem_forward(ptr(images), n, H, W, ptr(wpack), ptr(st_b), ptr(out), STEM_STORE | STEM_EPILOGUE, None, sp),
               "dns_stem_forward")
     return out
+
+
+# ----------------------------------------------------------------------------- LPIPS (csrc/lpips.hip, csrc/conv_plan.hpp)
+CONV_RELU, CONV_SCALE_INPUT = 1, 2                      # include/dns_hip.h: flags of dns_conv_cl
+LPIPS_MIN_SIDE = 31                                     # smaller images leave the second pool empty
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+# AlexNet `features`: (state-dict index, Cin, Cout, kernel, stride, pad, pooled input)
+LPIPS_LAYERS = ((0, 3, 64, 11, 4, 2, False), (3, 64, 192, 5, 1, 2, True), (6, 192, 384, 3, 1, 1, True),
+                (8, 384, 256, 3, 1, 1, False), (10, 256, 256, 3, 1, 1, False))
+LPIPS_METHODS = ("fused", "torch")
+# what ``method=None`` means for device tensors: at one pair of 680 x 1200 the fused kernels are slower than the library's
+# convolutions (1.54 against 1.27 ms); "fused" is the choice for fixed bits, batches and no first-call search
+LPIPS_DEFAULT = "torch"
+
+
+def conv_out_extent(size: int, ks: int, stride: int, pad: int) -> int:
+    return (int(size) + 2 * int(pad) - int(ks)) // int(stride) + 1
+
+
+def pool_out_extent(size: int) -> int:
+    """max pool 3x3, stride 2, no padding, floor mode"""
+    return (int(size) - 3) // 2 + 1
+
+
+def lpips_feature_shapes(H: int, W: int):
+    """[(h, w, C)] of the five LPIPS features of an H x W image."""
+    out, h, w = [], int(H), int(W)
+    for _, _, cout, ks, stride, pad, pooled in LPIPS_LAYERS:
+        if pooled:
+            h, w = pool_out_extent(h), pool_out_extent(w)
+        h, w = conv_out_extent(h, ks, stride, pad), conv_out_extent(w, ks, stride, pad)
+        out.append((h, w, cout))
+    return out
+
+
+def conv_pack(weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    """The packed weight image of ``dns_conv_cl`` (include/dns_hip.h) for ``weight`` [Cout,Cin,k,k] on the device:
+    [Cout/64][chunks][k per chunk, padded to even][64], built by torch ops, no read-back."""
+    cout, cin, ks, ks2 = (int(v) for v in weight.shape)
+    shape = (C.c_uint32 * 4)()
+    check(_rawlib.dns_conv_pack_shape(cin, cout, ks, int(stride), int(pad), shape), "dns_conv_pack_shape")
+    cb, chunks, kc_pad, ck = (int(v) for v in shape)
+    ncs = cin // ck
+    w = weight.detach().float().reshape(cb, 64, ncs, ck, ks, ks).permute(0, 4, 2, 5, 3, 1)       # cb, ky, cs, kx, c, o
+    pack = torch.zeros(cb, chunks, kc_pad, 64, device=weight.device)
+    pack[:, :, :ks * ck] = w.reshape(cb, ks * ncs, ks * ck, 64)
+    return pack.contiguous()
+
+
+def _conv_arguments(who, x, weight, bias, stride, pad):
+    for t in (x, weight) + ((bias,) if bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: every tensor must be on the GPU (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: every tensor must be float32, got {t.dtype}")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"{who}: x must be a contiguous channels-last [n,H,W,Cin] tensor, got {tuple(x.shape)}")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[1] != x.shape[3]:
+        raise ValueError(f"{who}: weight must be [Cout,{int(x.shape[3])},k,k], got {tuple(weight.shape)}")
+    cout, cin, ks = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+    if bias is not None and (tuple(bias.shape) != (cout,) or not bias.is_contiguous()):
+        raise ValueError(f"{who}: bias must be a contiguous [{cout}] tensor, got {tuple(bias.shape)}")
+    n, H, W = (int(v) for v in x.shape[:3])
+    stride, pad = int(stride), int(pad)
+    if cout % 64 != 0 or not (1 <= ks <= 11) or not (1 <= stride <= 4) or not (0 <= pad < ks):
+        raise ValueError(f"{who}: Cout {cout} must be a multiple of 64, the kernel {ks} at most 11, the stride {stride} at most 4 and "
+                         f"the padding {pad} below the kernel size")
+    if n < 1 or H + 2 * pad < ks or W + 2 * pad < ks:
+        raise ValueError(f"{who}: x {tuple(x.shape)} is empty or smaller than the kernel")
+    return n, H, W, cin, cout, ks, stride, pad
+
+
+def _launch_conv(x, n, H, W, cin, wpack, bias, cout, ks, stride, pad, flags, sp):
+    h, w = conv_out_extent(H, ks, stride, pad), conv_out_extent(W, ks, stride, pad)
+    out = torch.empty(n, h, w, cout, device=x.device)
+    check(lib.dns_conv_cl(ptr(x), n, H, W, cin, ptr(wpack), ptr(bias), cout, ks, stride, pad, flags, ptr(out), sp), "dns_conv_cl")
+    return out
+
+
+def conv_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int = 1, pad: int = 0, relu: bool = True, *,
+            scale_input: bool = False, wpack: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Channels-last convolution + bias + optional ReLU (keeping a NaN): ``x`` [n,H,W,Cin] fp32, ``weight`` [Cout,Cin,k,k] (Cout a
+    multiple of 64, k <= 11, stride <= 4, pad < k) -> [n,h,w,Cout]; exact fp32 products and fp32 accumulation in a fixed order, so
+    the bits of an image's map depend on the image and the parameters alone.  ``scale_input``: the LPIPS input scaling
+    (include/dns_hip.h) is applied to the 3-channel ``x`` as it is read, the zero padding staying zero.  ``wpack``:
+    ``conv_pack(weight, stride, pad)`` where the caller keeps it.  ValueError for CPU tensors and refused shapes, before any launch."""
+    n, H, W, cin, cout, ks, stride, pad = _conv_arguments("conv_cl", x, weight, bias, stride, pad)
+    if scale_input and cin != 3:
+        raise ValueError(f"conv_cl: scale_input is the scaling of a 3-channel image, x has {cin} channels")
+    if wpack is None:
+        wpack = conv_pack(weight, stride, pad)
+    flags = (CONV_RELU if relu else 0) | (CONV_SCALE_INPUT if scale_input else 0)
+    return _launch_conv(x.detach(), n, H, W, cin, wpack, None if bias is None else bias.detach(), cout, ks, stride, pad, flags,
+                        stream_ptr())
+
+
+def _launch_pool(x, sp):
+    n, h, w, c = (int(v) for v in x.shape)
+    out = torch.empty(n, pool_out_extent(h), pool_out_extent(w), c, device=x.device)
+    check(lib.dns_max_pool_cl(ptr(x), n, h, w, c, ptr(out), sp), "dns_max_pool_cl")
+    return out
+
+
+def max_pool_cl(x: torch.Tensor) -> torch.Tensor:
+    """Max pool 3x3, stride 2, no padding, floor mode, of channels-last ``x`` [n,h,w,C] fp32 (C a multiple of 4, sides >= 3) ->
+    [n,(h-3)//2+1,(w-3)//2+1,C]; a NaN in a window wins, as in F.max_pool2d."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("max_pool_cl: x must be on the GPU (there is no CPU fallback)")
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"max_pool_cl: x must be a contiguous float32 [n,h,w,C] tensor, got {x.dtype} {tuple(x.shape)}")
+    n, h, w, c = (int(v) for v in x.shape)
+    if n < 1 or h < 3 or w < 3 or c < 4 or c % 4 != 0:
+        raise ValueError(f"max_pool_cl: x {tuple(x.shape)}: sides must be at least 3 and C a multiple of 4")
+    return _launch_pool(x.detach(), stream_ptr())
+
+
+def _launch_head(fa, fb, lin, F, h, w, c, sp):
+    part = torch.empty(F, int(_rawlib.dns_lpips_head_blocks(h, w)), dtype=torch.float64, device=fa.device)
+    check(lib.dns_lpips_head(ptr(fa), ptr(fb), ptr(lin), F, h, w, c, ptr(part), sp), "dns_lpips_head")
+    return part
+
+
+def _launch_finish(parts, hs, ws, F, sp):
+    L = len(parts)
+    lp = torch.empty(F, dtype=torch.float64, device=parts[0].device)
+    layers = torch.empty(F, L, dtype=torch.float64, device=parts[0].device)
+    pa = (C.c_void_p * L)(*[int(p.data_ptr()) for p in parts])
+    check(lib.dns_lpips_finish(pa, (C.c_uint32 * L)(*hs), (C.c_uint32 * L)(*ws), L, F, ptr(lp), ptr(layers), sp), "dns_lpips_finish")
+    return lp, layers
+
+
+def lpips_head(feat_pred: torch.Tensor, feat_gt: torch.Tensor, lin: torch.Tensor) -> torch.Tensor:
+    """One layer of the LPIPS head: features [F,h,w,C] fp32 channels-last of the two images (C a multiple of 64, at most 512) and
+    ``lin`` [C] -> d [F] float64 on the device: the mean over pixels of sum_c lin_c (n(f_pred)_c - n(f_gt)_c)^2,
+    n(f) = f / (|f| + 1e-10), in float64 from the fp32 features, every sum in a fixed order."""
+    for t in (feat_pred, feat_gt, lin):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("lpips_head: every tensor must be on the GPU (there is no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("lpips_head: every tensor must be contiguous float32")
+    if feat_pred.dim() != 4 or feat_pred.shape != feat_gt.shape:
+        raise ValueError(f"lpips_head: features must be two [F,h,w,C] tensors, got {tuple(feat_pred.shape)} and {tuple(feat_gt.shape)}")
+    F, h, w, c = (int(v) for v in feat_pred.shape)
+    if F < 1 or F > 65535 or h < 1 or w < 1 or c % 64 != 0 or not (64 <= c <= 512) or tuple(lin.shape) != (c,):
+        raise ValueError(f"lpips_head: features {tuple(feat_pred.shape)}, lin {tuple(lin.shape)}: C must be a multiple of 64 up to 512 "
+                         f"and lin [C]")
+    sp = stream_ptr()
+    part = _launch_head(feat_pred.detach(), feat_gt.detach(), lin.detach(), F, h, w, c, sp)
+    return _launch_finish([part], [h], [w], F, sp)[1][:, 0]
+
+
+class LpipsWeights:
+    """The parameters of LPIPS (AlexNet): ``convs`` = five (weight [Cout,Cin,k,k], bias [Cout]) pairs, ``lins`` = five [C] vectors,
+    fp32.  ``on(device)`` returns (and keeps) the copies on a device together with the packed weight images of the fused path, made
+    once per device."""
+
+    def __init__(self, convs, lins):
+        convs = [(torch.as_tensor(w).detach().float().contiguous(), torch.as_tensor(b).detach().float().contiguous()) for w, b in convs]
+        lins = [torch.as_tensor(l).detach().float().reshape(-1).contiguous() for l in lins]
+        if len(convs) != 5 or len(lins) != 5:
+            raise ValueError(f"LpipsWeights: five convolutions and five lin vectors, got {len(convs)} and {len(lins)}")
+        for l, ((w, b), lin, (_, cin, cout, ks, _, _, _)) in enumerate(zip(convs, lins, LPIPS_LAYERS)):
+            if tuple(w.shape) != (cout, cin, ks, ks) or tuple(b.shape) != (cout,) or tuple(lin.shape) != (cout,):
+                raise ValueError(f"LpipsWeights: layer {l}: weight {tuple(w.shape)}, bias {tuple(b.shape)}, lin {tuple(lin.shape)} are "
+                                 f"not [{cout},{cin},{ks},{ks}], [{cout}], [{cout}]")
+        self.convs, self.lins = convs, lins
+        self._on = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        hit = self._on.get(device)
+        if hit is None:
+            convs = [(w.to(device), b.to(device)) for w, b in self.convs]
+            lins = [l.to(device) for l in self.lins]
+            packs = None
+            if device.type == "cuda":
+                packs = [conv_pack(w, stride, pad) for (w, _), (_, _, _, _, stride, pad, _) in zip(convs, LPIPS_LAYERS)]
+            hit = self._on[device] = (convs, lins, packs)
+        return hit
+
+
+def _lpips_arguments(pred, gt, weights):
+    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
+        raise ValueError("lpips: pred and gt must be tensors")
+    if pred.shape != gt.shape:
+        raise ValueError(f"lpips: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+    if pred.dim() not in (3, 4) or pred.shape[-1] != 3:
+        raise ValueError(f"lpips: images must be [H,W,3] or [F,H,W,3], got {tuple(pred.shape)}")
+    if pred.device != gt.device:
+        raise ValueError("lpips: pred and gt must be on one device")
+    if not isinstance(weights, LpipsWeights):
+        raise ValueError("lpips: weights must be an LpipsWeights (evaluation.load_lpips_weights)")
+    F, H, W = (1,) + tuple(pred.shape[:2]) if pred.dim() == 3 else tuple(pred.shape[:3])
+    if min(H, W) < LPIPS_MIN_SIDE:
+        raise ValueError(f"lpips: images of {H} x {W}: both sides must be at least {LPIPS_MIN_SIDE} (the second 3x3 pool would be empty)")
+    if F == 0 or 2 * F > 65535:
+        raise ValueError(f"lpips: {F} pairs (1..32767)")
+    p = pred.detach().float().contiguous().view(F, H, W, 3)
+    g = gt.detach().float().contiguous().view(F, H, W, 3)
+    return p, g, int(F), int(H), int(W)
+
+
+def _lpips_torch(p, g, weights, channels_last=False):
+    """The definition of include/dns_hip.h out of torch ops in fp32 (F.conv2d, F.max_pool2d), as the lpips package evaluates it.
+    ``channels_last``: the library's other memory format (tools/time_lpips.py times both).  The library's convolutions are free to
+    round an image differently at another batch position or in another call, so identical images need not give exactly 0 here."""
+    import torch.nn.functional as Fn
+    convs, lins, _ = weights.on(p.device)
+    shift = torch.tensor(LPIPS_SHIFT, device=p.device).view(1, 3, 1, 1)
+    scale = torch.tensor(LPIPS_SCALE, device=p.device).view(1, 3, 1, 1)
+    F = p.shape[0]
+    x = torch.cat((p, g)).permute(0, 3, 1, 2)
+    if channels_last:
+        x = x.contiguous(memory_format=torch.channels_last)
+    x = torch.where(x < 0, torch.zeros_like(x), torch.where(x > 1, torch.ones_like(x), x))       # a NaN stays
+    x = (2.0 * x - 1.0 - shift) / scale
+    ds = []
+    for (w, b), lin, (_, _, _, _, stride, pad, pooled) in zip(convs, lins, LPIPS_LAYERS):
+        if pooled:
+            x = Fn.max_pool2d(x, 3, 2)
+        x = torch.relu(Fn.conv2d(x, w, b, stride=stride, padding=pad))                           # torch's relu keeps a NaN
+        n = x / (torch.sqrt((x * x).sum(1, keepdim=True)) + 1e-10)
+        ds.append(((n[:F] - n[F:]) ** 2 * lin.view(1, -1, 1, 1)).sum(1).flatten(1).mean(1))
+    layers = torch.stack(ds, 1).double()
+    return layers.sum(1), layers
+
+
+def lpips_launch(pred: torch.Tensor, gt: torch.Tensor, weights: LpipsWeights, method: Optional[str] = None):
+    """``lpips`` without a host read: -> (lpips [F] float64, layers [F,5] float64) on the tensors' device; F = 1 for [H,W,3] images."""
+    if method is not None and method not in LPIPS_METHODS:
+        raise ValueError(f"lpips: method must be None, 'fused' or 'torch', got {method!r}")
+    p, g, F, H, W = _lpips_arguments(pred, gt, weights)
+    if method is None:
+        method = LPIPS_DEFAULT if p.is_cuda else "torch"
+    if method == "torch":
+        return _lpips_torch(p, g, weights)
+    require_cuda(p, g)
+    convs, lins, packs = weights.on(p.device)
+    sp = stream_ptr()
+    x = torch.cat((p, g))                                 # pred and gt as one batch of 2F images: twice the tiles per launch
+    n, h, w = 2 * F, H, W
+    parts, hs, ws = [], [], []
+    for l, ((wt, b), lin, pack, (_, cin, cout, ks, stride, pad, pooled)) in enumerate(zip(convs, lins, packs, LPIPS_LAYERS)):
+        if pooled:
+            x = _launch_pool(x, sp)
+            h, w = pool_out_extent(h), pool_out_extent(w)
+        x = _launch_conv(x, n, h, w, cin, pack, b, cout, ks, stride, pad, CONV_RELU | (CONV_SCALE_INPUT if l == 0 else 0), sp)
+        h, w = int(x.shape[1]), int(x.shape[2])
+        parts.append(_launch_head(x[:F], x[F:], lin, F, h, w, cout, sp))
+        hs.append(h), ws.append(w)
+    return _launch_finish(parts, hs, ws, F, sp)
+
+
+def lpips(pred: torch.Tensor, gt: torch.Tensor, weights: LpipsWeights, method: Optional[str] = None):
+    """LPIPS (AlexNet; the definition of include/dns_hip.h: lpips 0.1.4 as torchmetrics 0.11.1 calls it with ``normalize=True``, what
+    eval_2d.py:304 evaluates) of image pairs pred, gt [H,W,3] or [F,H,W,3] fp32 in [0,1], in the project's image layout ->
+    {"lpips": float64 [F] (0-d for one image), "layers": float64 [F,5] ([5])} on the tensors' device.  ``method="fused"``: the HIP
+    kernels (convolutions in exact fp32 in a fixed order, head in float64; the same bits for every call and every batch);
+    ``method="torch"``: the same definition composed of F.conv2d / F.max_pool2d in fp32, which also runs on CPU tensors (on the
+    device its bits are the library's: identical images need not give exactly 0, and its first call searches for algorithms for
+    seconds); None: ``LPIPS_DEFAULT`` for device tensors ("torch": faster at one frame-size pair, "fused" is faster from a few pairs
+    on), "torch" for CPU tensors.  Sides below 31, mismatched shapes, a last dimension other
+    than 3 and, for "fused", CPU tensors raise ValueError before anything is launched.
+
+    The weights come from the caller (``evaluation.load_lpips_weights``); the arithmetic is held to a float64 restatement of the
+    published definition (tests/lpips_ref.py), not to values written by the lpips package, which is not available here."""
+    single = isinstance(pred, torch.Tensor) and pred.dim() == 3
+    val, layers = lpips_launch(pred, gt, weights, method)
+    if single:
+        val, layers = val[0], layers[0]
+    return {"lpips": val, "layers": layers}

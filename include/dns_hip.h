@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 23
+#define DNS_ABI_VERSION 24
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -940,6 +940,50 @@ int dns_frame_codes(const float* pts, uint32_t P, const float* w2c, const float*
                     const float* feat, uint32_t C, int h, int w, int H, int W, const uint8_t* keep, const double* bound,
                     uint32_t n_bins, const float* params, uint32_t n_neurons, uint32_t n_hidden_layers, uint32_t hid,
                     float* ws, uint64_t ws_floats, float* out, uint32_t ld_out, uint32_t tile_pts, void* stream);
+
+/* ---- LPIPS (eval_2d.py:81-82,304 of the reference: torchmetrics 0.11.1's LearnedPerceptualImagePatchSimilarity(net_type='alex',
+ * normalize=True) over lpips 0.1.4; csrc/lpips.hip, csrc/conv_plan.hpp; ABI v24) ---------------------------------------------
+ * The definition, per image pair pred, gt [H,W,3] fp32 (the project's channels-last layout):
+ *   1. input scaling: x = clamp(x, 0, 1); x = 2x - 1; x = (x - shift_c) / scale_c, shift = (-0.030, -0.088, -0.188),
+ *      scale = (0.458, 0.448, 0.450).  A NaN stays a NaN.  The first convolution's zero padding is zero IN THIS SCALED SPACE.
+ *   2. tower = torchvision AlexNet `features`; every convolution has a bias and is followed by ReLU; the features are
+ *        f0 = conv1(x)         3 ->  64, 11x11, stride 4, pad 2
+ *        f1 = conv2(pool(f0)) 64 -> 192,  5x5,  pad 2
+ *        f2 = conv3(pool(f1)) 192 -> 384, 3x3,  pad 1
+ *        f3 = conv4(f2)      384 -> 256,  3x3,  pad 1
+ *        f4 = conv5(f3)      256 -> 256,  3x3,  pad 1
+ *      pool = max 3x3, stride 2, no padding, floor mode.  ReLU and max keep a NaN.
+ *   3. head, per layer l and pixel: n(f) = f / (sqrt(sum_c f_c^2) + 1e-10);
+ *      d_l = mean over pixels of sum_c lin_l[c] (n(f_pred)_c - n(f_gt)_c)^2.  lin_l has no bias; there is no dropout.
+ *   4. lpips = sum_l d_l.
+ * Sides below 31 leave the second pool empty and are refused.  The arithmetic is pinned to a float64 restatement of this definition
+ * (tests/lpips_ref.py), not to a file written by the lpips package: neither it nor any pretrained weight is part of the repository.
+ *
+ * dns_conv_cl: channels-last convolution + bias (NULL = none) + ReLU (DNS_CONV_RELU, keeping a NaN): x [n,H,W,Cin] ->
+ * out [n,h,w,Cout], h = (H + 2 pad - ks) / stride + 1, square kernel ks <= 11, stride <= 4, pad < ks, Cout a multiple of 64; exact
+ * fp32 products, fp32 accumulation from 0 in (ky, channel slice, kx, c) order, then + bias: the bits of an image's map depend on
+ * nothing but the image, wpack and bias.  wpack: the packed weight image [shape[0]][shape[1]][shape[2]][64] of dns_conv_pack_shape
+ * (shape = {Cout / 64, chunks, k per chunk padded to even, CK channels per chunk}): chunk = ky (Cin / CK) + cs; element
+ * (cb, chunk, kx CK + c, o) = weight[cb 64 + o][cs CK + c][ky][kx]; rows past ks CK zero; 16-byte aligned.  x 16-byte aligned where
+ * Cin % 4 == 0; out 128-byte aligned.  DNS_CONV_SCALE_INPUT (Cin = 3 only): step 1 is applied to x as it is staged, the padding
+ * staying 0.  No atomics.
+ * dns_max_pool_cl: x [n,h,w,C] -> out [n,(h-3)/2+1,(w-3)/2+1,C], C a multiple of 4, both 16-byte aligned; a NaN in a window wins.
+ * dns_lpips_head: one layer: fa, fb [F,h,w,C] (C a multiple of 64, <= 512), lin [C] -> partials [F][dns_lpips_head_blocks(h, w)]
+ * float64, one per workgroup (64 consecutive pixels), everything after the fp32 features in float64; a pixel whose features are all
+ * zero contributes 0.  dns_lpips_finish: partials / h / w [host arrays of n_layers <= 5 entries]: adds each layer's partials in
+ * index order, divides by h w -> layers [F][n_layers]; lpips [F] = their sum in layer order.  No floating-point atomics: the same
+ * bits for every call and every batch. */
+#define DNS_CONV_RELU 1u
+#define DNS_CONV_SCALE_INPUT 2u
+int dns_conv_pack_shape(uint32_t Cin, uint32_t Cout, uint32_t ks, uint32_t stride, uint32_t pad, uint32_t* shape);
+int dns_conv_cl(const float* x, uint32_t n, uint32_t H, uint32_t W, uint32_t Cin, const float* wpack, const float* bias, uint32_t Cout,
+                uint32_t ks, uint32_t stride, uint32_t pad, uint32_t flags, float* out, void* stream);
+int dns_max_pool_cl(const float* x, uint32_t n, uint32_t h, uint32_t w, uint32_t C, float* out, void* stream);
+uint32_t dns_lpips_head_blocks(uint32_t h, uint32_t w);
+int dns_lpips_head(const float* fa, const float* fb, const float* lin, uint32_t F, uint32_t h, uint32_t w, uint32_t C, double* partials,
+                   void* stream);
+int dns_lpips_finish(const double* const* partials, const uint32_t* h, const uint32_t* w, uint32_t n_layers, uint32_t F, double* lpips,
+                     double* layers, void* stream);
 
 #ifdef __cplusplus
 }
