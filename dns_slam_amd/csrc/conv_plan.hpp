@@ -17,6 +17,7 @@
 // element (cb, chunk, kx CK + c, o) = weight[cb 64 + o][cs CK + c][ky][kx].
 #pragma once
 #include <stdint.h>
+#include "conv_tile.hpp"
 
 #if defined(__HIPCC__)
 #define DNS_CONV_HD __host__ __device__ inline
@@ -27,11 +28,12 @@
 namespace dns {
 namespace convp {
 
-constexpr int THREADS = 256;                       // 4 waves
-constexpr int WAVES = 4;
-constexpr int TILE_W = 32;                         // output pixels of one matrix tile (M = 32) along x
-constexpr int ROWS_PER_WAVE = 2;                   // matrix tiles per wave: consecutive output rows
-constexpr int TILE_H = WAVES * ROWS_PER_WAVE;      // 8 output rows per workgroup
+// the workgroup shape and the accumulator map: conv_tile.hpp's, shared with the image stem (stem_tile.hpp)
+using convt::THREADS; using convt::WAVES; using convt::TILE_W; using convt::ROWS_PER_WAVE; using convt::TILE_H;
+using convt::row_of; using convt::acc_pixel; using convt::acc_channel;
+#if defined(__HIPCC__)
+using convt::f32x16; using convt::relu;
+#endif
 constexpr int NB = 64;                             // output channels per workgroup: two N blocks of 32
 constexpr int LDS_FLOATS = 15360;                  // 60 KB of static LDS: two workgroups per CU
 constexpr int LDS_BYTES = LDS_FLOATS * 4;
@@ -165,12 +167,6 @@ DNS_CONV_HD int64_t stage_src(const Plan& p, const Tile& t, int ky, int cs, int 
 // A operand: rows[pixel_base(ly, lx) + k_offset(kx, c)] for the output pixel (ly, lx) of the tile, kx < ks, c < CK
 DNS_CONV_HD int pixel_base(const Plan& p, int ly, int lx) { return ly * p.ROW_STRIDE + p.stride * lx * p.CKP; }
 DNS_CONV_HD int k_offset(const Plan& p, int kx, int c) { return kx * p.CKP + c; }
-
-// Accumulator element -> output: wave `wave`'s matrix tile `mt` is the tile's output row row_of(wave, mt); register r of lane l holds
-// the pixel acc_pixel(r, l) of that row and the channel acc_channel(l) (+ 32 for the second N block): the C/D map of the 32x32 forms
-DNS_CONV_HD int row_of(int wave, int mt) { return wave * ROWS_PER_WAVE + mt; }
-DNS_CONV_HD int acc_pixel(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-DNS_CONV_HD int acc_channel(int lane) { return lane & 31; }
 
 // ---- max pool 3x3 stride 2, no padding, floor mode
 DNS_CONV_HD int pool_extent(int e) { return e < 3 ? 0 : (e - 3) / 2 + 1; }

@@ -8,111 +8,56 @@
 // point), one lane per channel.  Forward only: the code carries no gradient (frozen stem; rounding blocks the pose path).
 // Memory-bound gather: 4 * C * 4 bytes read per (frame, point), served from L2 / Infinity Cache.
 #include "common.hpp"
+#include "dev_feature.hpp"
 
 namespace dns {
 
-struct Mat3 {
-  float k[9];
-};
-
+// One wave64 per (reference, point) pair, one lane per channel: any C, any alignment.  The projection, the taps and their sum are
+// dev_feature.hpp's.  FRAMES: the in-loop form of the branch (slams/mapping.py:532-557, slams/tracking.py:162-165 inside every
+// optimise iteration), one launch for the K target frames of an iteration: reference rr = f R + r looks at the points of frame
+// f = rr / R (pts [K, P_f, 3]).  Besides the code -- written at a row stride (straight into the Merge network's input row, behind
+// the OneBlob columns) -- it writes the RELATIVE point pts - o_rr that Decoder.merge encodes (utils/common.py:675) and no mask.
+template <bool FRAMES>
 __global__ __launch_bounds__(256) void feature_gather_kernel(const float* __restrict__ pts, const float* __restrict__ w2c,
-                                                             Mat3 K, const float* __restrict__ feat, uint32_t R, uint32_t P,
-                                                             uint32_t C, int h, int w, int H, int W,
-                                                             float* __restrict__ code, uint8_t* __restrict__ mask_out) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t pair = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pair >= (uint64_t)R * P) return;
-  const uint32_t r = (uint32_t)(pair / P), p = (uint32_t)(pair % P);
-  const float x = pts[(size_t)p * 3], y = pts[(size_t)p * 3 + 1], z = pts[(size_t)p * 3 + 2];
-  const float* m = w2c + 16 * r;
-  // camera-frame point, y and z flipped (utils/common.py:650-652)
-  const float cx_ = fmaf(m[3], 1.0f, fmaf(m[2], z, fmaf(m[1], y, m[0] * x)));
-  const float cy_ = -fmaf(m[7], 1.0f, fmaf(m[6], z, fmaf(m[5], y, m[4] * x)));
-  const float cz_ = -fmaf(m[11], 1.0f, fmaf(m[10], z, fmaf(m[9], y, m[8] * x)));
-  const float q0 = fmaf(K.k[2], cz_, fmaf(K.k[1], cy_, K.k[0] * cx_));
-  const float q1 = fmaf(K.k[5], cz_, fmaf(K.k[4], cy_, K.k[3] * cx_));
-  const float q2 = fmaf(K.k[8], cz_, fmaf(K.k[7], cy_, K.k[6] * cx_));
-  const float u = rintf(q0 / (q2 + 1e-5f));            // torch.round: half to even
-  const float v = rintf(q1 / (q2 + 1e-5f));
-  const bool ok = (u > 0.f) && (u < (float)(W - 1)) && (v > 0.f) && (v < (float)(H - 1)) && (cz_ > 0.f);
-  if (lane == 0 && mask_out) mask_out[pair] = ok ? 1 : 0;
-  float* out = code + pair * C;
-  if (!ok) {
-    for (uint32_t c = lane; c < C; c += 64) out[c] = 0.f;
-    return;
-  }
-  // F.interpolate(..., align_corners=True) evaluated at the integer pixel (u, v)
-  const float sx_scale = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-  const float sy_scale = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-  const float sx = __fmul_rn(sx_scale, u), sy = __fmul_rn(sy_scale, v);
-  const int x0 = (int)sx, y0 = (int)sy;
-  const float lx = sx - (float)x0, ly = sy - (float)y0;
-  const int x1 = x0 + (x0 < w - 1 ? 1 : 0), y1 = y0 + (y0 < h - 1 ? 1 : 0);
-  const float* f = feat + (size_t)r * h * w * C;
-  const float* f00 = f + ((size_t)y0 * w + x0) * C;
-  const float* f01 = f + ((size_t)y0 * w + x1) * C;
-  const float* f10 = f + ((size_t)y1 * w + x0) * C;
-  const float* f11 = f + ((size_t)y1 * w + x1) * C;
-  for (uint32_t c = lane; c < C; c += 64)
-    out[c] = (1.f - ly) * ((1.f - lx) * f00[c] + lx * f01[c]) + ly * ((1.f - lx) * f10[c] + lx * f11[c]);
-}
-
-
-// ---- the in-loop form of the branch (slams/mapping.py:532-557, slams/tracking.py:162-165 inside every optimise iteration) ----
-// One launch for the K target frames of an iteration: reference rr = f R + r looks at the points of frame f = rr / R
-// (pts [K, P_f, 3]).  Besides the code -- written at a row stride (straight into the Merge network's input row, behind the
-// OneBlob columns) -- it writes the RELATIVE point pts - o_rr that Decoder.merge encodes (utils/common.py:675).
-__global__ __launch_bounds__(256) void feature_gather_frames_kernel(const float* __restrict__ pts, const float* __restrict__ w2c,
-                                                                    const float* __restrict__ origin, Mat3 K,
-                                                                    const float* __restrict__ feat, uint32_t n_ref_total,
-                                                                    uint32_t R, uint32_t Pf, uint32_t C, int h, int w, int H, int W,
-                                                                    float* __restrict__ code, uint32_t ld_code,
-                                                                    float* __restrict__ rel_out) {
+                                                             const float* __restrict__ origin, Mat3 K,
+                                                             const float* __restrict__ feat, uint32_t n_ref_total, uint32_t R,
+                                                             uint32_t Pf, uint32_t C, int h, int w, int H, int W,
+                                                             float* __restrict__ code, uint32_t ld_code,
+                                                             float* __restrict__ rel_out, uint8_t* __restrict__ mask_out) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t pair = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pair >= (uint64_t)n_ref_total * Pf) return;
   const uint32_t rr = (uint32_t)(pair / Pf), pl = (uint32_t)(pair % Pf);
-  const size_t p = (size_t)(rr / R) * Pf + pl;
+  const size_t p = FRAMES ? (size_t)(rr / R) * Pf + pl : (size_t)pl;
   const float x = pts[p * 3], y = pts[p * 3 + 1], z = pts[p * 3 + 2];
-  const float* m = w2c + 16 * rr;
-  const float cx_ = fmaf(m[3], 1.0f, fmaf(m[2], z, fmaf(m[1], y, m[0] * x)));
-  const float cy_ = -fmaf(m[7], 1.0f, fmaf(m[6], z, fmaf(m[5], y, m[4] * x)));
-  const float cz_ = -fmaf(m[11], 1.0f, fmaf(m[10], z, fmaf(m[9], y, m[8] * x)));
-  const float q0 = fmaf(K.k[2], cz_, fmaf(K.k[1], cy_, K.k[0] * cx_));
-  const float q1 = fmaf(K.k[5], cz_, fmaf(K.k[4], cy_, K.k[3] * cx_));
-  const float q2 = fmaf(K.k[8], cz_, fmaf(K.k[7], cy_, K.k[6] * cx_));
-  const float u = rintf(q0 / (q2 + 1e-5f));
-  const float v = rintf(q1 / (q2 + 1e-5f));
-  const bool ok = (u > 0.f) && (u < (float)(W - 1)) && (v > 0.f) && (v < (float)(H - 1)) && (cz_ > 0.f);
-  if (lane < 3u && rel_out) {
-    const float c = lane == 0 ? x : (lane == 1 ? y : z);
-    rel_out[pair * 3 + lane] = c - origin[rr * 3 + lane];
+  const FeaturePixel q = feature_project(w2c + 16 * rr, K, x, y, z, H, W);
+  if (FRAMES) {
+    if (lane < 3u && rel_out) {
+      const float c = lane == 0 ? x : (lane == 1 ? y : z);
+      rel_out[pair * 3 + lane] = c - origin[rr * 3 + lane];
+    }
+  } else if (lane == 0 && mask_out) {
+    mask_out[pair] = q.ok ? 1 : 0;
   }
   float* out = code + pair * ld_code;
-  if (!ok) {
+  if (!q.ok) {
     for (uint32_t c = lane; c < C; c += 64) out[c] = 0.f;
     return;
   }
-  const float sx_scale = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-  const float sy_scale = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-  const float sx = __fmul_rn(sx_scale, u), sy = __fmul_rn(sy_scale, v);
-  const int x0 = (int)sx, y0 = (int)sy;
-  const float lx = sx - (float)x0, ly = sy - (float)y0;
-  const int x1 = x0 + (x0 < w - 1 ? 1 : 0), y1 = y0 + (y0 < h - 1 ? 1 : 0);
+  const FeatureTaps t = feature_taps(q.u, q.v, h, w, H, W);
   const float* f = feat + (size_t)rr * h * w * C;
-  const float* f00 = f + ((size_t)y0 * w + x0) * C;
-  const float* f01 = f + ((size_t)y0 * w + x1) * C;
-  const float* f10 = f + ((size_t)y1 * w + x0) * C;
-  const float* f11 = f + ((size_t)y1 * w + x1) * C;
-  for (uint32_t c = lane; c < C; c += 64)
-    out[c] = (1.f - ly) * ((1.f - lx) * f00[c] + lx * f01[c]) + ly * ((1.f - lx) * f10[c] + lx * f11[c]);
+  const float* f00 = f + ((size_t)t.y0 * w + t.x0) * C;
+  const float* f01 = f + ((size_t)t.y0 * w + t.x1) * C;
+  const float* f10 = f + ((size_t)t.y1 * w + t.x0) * C;
+  const float* f11 = f + ((size_t)t.y1 * w + t.x1) * C;
+  feature_row<64>(f00, f01, f10, f11, t.lx, t.ly, C, lane, out);
 }
 
-// The four-channel form of both kernels above (C % 4 == 0 and 16-byte aligned rows: the stem maps have 64 channels): 16 lanes
+// The four-channel form (C % 4 == 0 and 16-byte aligned rows: the stem maps have 64 channels): 16 lanes
 // per (reference, point) pair, one float4 of channels per lane -- a wave works on FOUR pairs, so the projection (the same ~40
 // vector instructions in every lane of a pair) is issued a quarter as often and every tap is one 16-byte load per lane.  The
-// one-lane-per-channel kernels were issue-bound at 64 channels (193 us per cfg3 iteration for 786 432 pairs; the 805 MB of taps
-// come out of L2 / MALL, 201 MB are written).  Same expressions per channel: same values.
+// one-lane-per-channel kernel was issue-bound at 64 channels (193 us per cfg3 iteration for 786 432 pairs; the 805 MB of taps
+// come out of L2 / MALL, 201 MB are written).  Same functions per channel: same values.
 template <bool FRAMES>
 __global__ __launch_bounds__(256) void feature_gather4_kernel(const float* __restrict__ pts, const float* __restrict__ w2c,
                                                               const float* __restrict__ origin, Mat3 K,
@@ -126,50 +71,28 @@ __global__ __launch_bounds__(256) void feature_gather4_kernel(const float* __res
   const uint32_t rr = (uint32_t)(pair / Pf), pl = (uint32_t)(pair % Pf);
   const size_t p = FRAMES ? (size_t)(rr / R) * Pf + pl : (size_t)pl;
   const float x = pts[p * 3], y = pts[p * 3 + 1], z = pts[p * 3 + 2];
-  const float* m = w2c + 16 * rr;
-  const float cx_ = fmaf(m[3], 1.0f, fmaf(m[2], z, fmaf(m[1], y, m[0] * x)));
-  const float cy_ = -fmaf(m[7], 1.0f, fmaf(m[6], z, fmaf(m[5], y, m[4] * x)));
-  const float cz_ = -fmaf(m[11], 1.0f, fmaf(m[10], z, fmaf(m[9], y, m[8] * x)));
-  const float q0 = fmaf(K.k[2], cz_, fmaf(K.k[1], cy_, K.k[0] * cx_));
-  const float q1 = fmaf(K.k[5], cz_, fmaf(K.k[4], cy_, K.k[3] * cx_));
-  const float q2 = fmaf(K.k[8], cz_, fmaf(K.k[7], cy_, K.k[6] * cx_));
-  const float u = rintf(q0 / (q2 + 1e-5f));
-  const float v = rintf(q1 / (q2 + 1e-5f));
-  const bool ok = (u > 0.f) && (u < (float)(W - 1)) && (v > 0.f) && (v < (float)(H - 1)) && (cz_ > 0.f);
+  const FeaturePixel q = feature_project(w2c + 16 * rr, K, x, y, z, H, W);
   if (FRAMES) {
     if (sub < 3u && rel_out) {
       const float c = sub == 0 ? x : (sub == 1 ? y : z);
       rel_out[pair * 3 + sub] = c - origin[rr * 3 + sub];
     }
   } else if (sub == 0 && mask_out) {
-    mask_out[pair] = ok ? 1 : 0;
+    mask_out[pair] = q.ok ? 1 : 0;
   }
   float4* out = reinterpret_cast<float4*>(code + pair * ld_code);
   const uint32_t C4 = C / 4u;
-  if (!ok) {
+  if (!q.ok) {
     for (uint32_t c = sub; c < C4; c += 16) out[c] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
-  const float sx_scale = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-  const float sy_scale = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-  const float sx = __fmul_rn(sx_scale, u), sy = __fmul_rn(sy_scale, v);
-  const int x0 = (int)sx, y0 = (int)sy;
-  const float lx = sx - (float)x0, ly = sy - (float)y0;
-  const int x1 = x0 + (x0 < w - 1 ? 1 : 0), y1 = y0 + (y0 < h - 1 ? 1 : 0);
+  const FeatureTaps t = feature_taps(q.u, q.v, h, w, H, W);
   const float* f = feat + (size_t)rr * h * w * C;
-  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)y0 * w + x0) * C);
-  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)y0 * w + x1) * C);
-  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)y1 * w + x0) * C);
-  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)y1 * w + x1) * C);
-  for (uint32_t c = sub; c < C4; c += 16) {
-    const float4 a = f00[c], b = f01[c], d = f10[c], e = f11[c];
-    float4 o;
-    o.x = (1.f - ly) * ((1.f - lx) * a.x + lx * b.x) + ly * ((1.f - lx) * d.x + lx * e.x);
-    o.y = (1.f - ly) * ((1.f - lx) * a.y + lx * b.y) + ly * ((1.f - lx) * d.y + lx * e.y);
-    o.z = (1.f - ly) * ((1.f - lx) * a.z + lx * b.z) + ly * ((1.f - lx) * d.z + lx * e.z);
-    o.w = (1.f - ly) * ((1.f - lx) * a.w + lx * b.w) + ly * ((1.f - lx) * d.w + lx * e.w);
-    out[c] = o;
-  }
+  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x0) * C);
+  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x1) * C);
+  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x0) * C);
+  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x1) * C);
+  feature_row<16>(f00, f01, f10, f11, t.lx, t.ly, C4, sub, out);
 }
 static bool gather4_ok(const float* feat, const float* code, uint32_t C, uint32_t ld_code) {
   return C % 4u == 0 && ld_code % 4u == 0 && (((uintptr_t)feat | (uintptr_t)code) & 15) == 0 && getenv("DNS_FEATURE_GATHER_LANES") == nullptr;
@@ -272,8 +195,8 @@ extern "C" int dns_feature_gather_frames(const float* pts, const float* w2c, con
     DNS_LAUNCH(feature_gather4_kernel<true>, dim3((uint32_t)((pairs + 15) / 16)), dim3(256), 0, (hipStream_t)stream, pts, w2c, origin,
                Km, feat, n_frames * R, R, pts_per_frame, C, h, w, H, W, code, ld_code, rel_out, (uint8_t*)nullptr);
   else
-    DNS_LAUNCH(feature_gather_frames_kernel, dim3((uint32_t)((pairs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pts, w2c, origin, Km,
-               feat, n_frames * R, R, pts_per_frame, C, h, w, H, W, code, ld_code, rel_out);
+    DNS_LAUNCH(feature_gather_kernel<true>, dim3((uint32_t)((pairs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pts, w2c, origin, Km,
+               feat, n_frames * R, R, pts_per_frame, C, h, w, H, W, code, ld_code, rel_out, (uint8_t*)nullptr);
   return check_launch("dns_feature_gather_frames");
 }
 
@@ -325,7 +248,7 @@ extern "C" int dns_feature_gather(const float* pts, const float* w2c, const floa
     DNS_LAUNCH(feature_gather4_kernel<false>, dim3((uint32_t)((pairs + 15) / 16)), dim3(256), 0, (hipStream_t)stream, pts, w2c,
                (const float*)nullptr, Km, feat, R, R, P, C, h, w, H, W, code, C, (float*)nullptr, mask);
   else
-    DNS_LAUNCH(feature_gather_kernel, dim3((uint32_t)((pairs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pts, w2c, Km,
-               feat, R, P, C, h, w, H, W, code, mask);
+    DNS_LAUNCH(feature_gather_kernel<false>, dim3((uint32_t)((pairs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pts, w2c,
+               (const float*)nullptr, Km, feat, R, R, P, C, h, w, H, W, code, C, (float*)nullptr, mask);
   return check_launch("dns_feature_gather");
 }

@@ -6,8 +6,8 @@
 //
 // A 256-thread workgroup owns tiles of up to 128 points (frame_codes_plan.hpp: 32 or 64 where the points are few) and keeps the Merge weight images in its LDS for all of
 // them (build_fwd_images, once).  Per tile:
-//   A  for every view: project, gather, OneBlob.  16 lanes per (point, view) pair and one float4 of channels per lane, the
-//      expressions of feature_gather4_kernel (feature.hip); the OneBlob columns of rel = p - o_r, normalised with the scene bound
+//   A  for every view: project, gather, OneBlob.  16 lanes per (point, view) pair and one float4 of channels per lane, as
+//      feature_gather4_kernel (feature.hip) on the functions of dev_feature.hpp; the OneBlob columns of rel = p - o_r, normalised with the scene bound
 //      in fp64 (dev_encode.hpp: the encoder's functions), go through an LDS tile and leave as contiguous float4 runs.  Both land
 //      in the workgroup's private slice of a global workspace (72 KB per view and 128 points; which cache holds it is not
 //      measured, and at a full grid the slices exceed L2: DESIGN 4.20), the way track_fused.inc hands rows
@@ -18,10 +18,11 @@
 // No atomics: a point's bits depend on the point, the views and the weights alone.
 //
 // Contraction: feature.hip and encode.hip are compiled with -ffp-contract=off, mlp_split.hip is not, and this unit must give the
-// bits of all three -- it is compiled like mlp_split.hip, and the projection, the taps and the normalisation carry the setting as
-// a function-level pragma (dev_encode.hpp's functions carry their own).
+// bits of all three -- it is compiled like mlp_split.hip, and the normalisation carries the setting as a function-level pragma
+// (the projection and the taps are dev_feature.hpp's functions, which carry their own, as dev_encode.hpp's do).
 #include "mlp_split.hpp"
 #include "dev_encode.hpp"
+#include "dev_feature.hpp"
 #include "frame_codes_plan.hpp"
 
 namespace dns {
@@ -30,10 +31,6 @@ namespace fc {
 // (explicit LDS pointers: see track_fused.inc -- a pointer into the dynamic LDS that went through arithmetic on a kernel
 //  argument is a generic pointer to hipcc)
 typedef __attribute__((address_space(3))) float* lds_fp;
-
-struct Mat3 {
-  float k[9];
-};
 
 struct Args {
   const float* pts;                          // [P,3]
@@ -53,49 +50,25 @@ struct Args {
   uint32_t* err;
 };
 
-// one (point, view) pair's code -> dst[0 .. C) (16-byte aligned), lane `sub` of the pair's 16: feature_gather4_kernel's
-// expressions (feature.hip:130-171).  Not valid, or not kept: zeros, and no tap is read.
+// one (point, view) pair's code -> dst[0 .. C) (16-byte aligned), lane `sub` of the pair's 16: what feature_gather4_kernel does
+// with dev_feature.hpp's functions.  Not valid, or not kept: zeros, and no tap is read.
 __device__ __forceinline__ void pair_code(const Args& a, uint32_t r, size_t p, bool kept, uint32_t sub, float* __restrict__ dst) {
-#pragma clang fp contract(off)
   const float x = a.pts[p * 3], y = a.pts[p * 3 + 1], z = a.pts[p * 3 + 2];
-  const float* m = a.w2c + 16 * r;
-  const float cx_ = fmaf(m[3], 1.0f, fmaf(m[2], z, fmaf(m[1], y, m[0] * x)));
-  const float cy_ = -fmaf(m[7], 1.0f, fmaf(m[6], z, fmaf(m[5], y, m[4] * x)));
-  const float cz_ = -fmaf(m[11], 1.0f, fmaf(m[10], z, fmaf(m[9], y, m[8] * x)));
-  const float q0 = fmaf(a.K.k[2], cz_, fmaf(a.K.k[1], cy_, a.K.k[0] * cx_));
-  const float q1 = fmaf(a.K.k[5], cz_, fmaf(a.K.k[4], cy_, a.K.k[3] * cx_));
-  const float q2 = fmaf(a.K.k[8], cz_, fmaf(a.K.k[7], cy_, a.K.k[6] * cx_));
-  const float u0 = rintf(q0 / (q2 + 1e-5f));
-  const float v0 = rintf(q1 / (q2 + 1e-5f));
   const int H = a.H, W = a.W, h = a.h, w = a.w;
-  const bool ok = kept && (u0 > 0.f) && (u0 < (float)(W - 1)) && (v0 > 0.f) && (v0 < (float)(H - 1)) && (cz_ > 0.f);
+  const FeaturePixel q = feature_project(a.w2c + 16 * r, a.K, x, y, z, H, W, kept);
   const uint32_t C = a.C, C4 = C / 4u;
   float4* out = reinterpret_cast<float4*>(dst);
-  if (!ok) {
+  if (!q.ok) {
     for (uint32_t c = sub; c < C4; c += 16) out[c] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
-  const float u = u0, v = v0;
-  const float sx_scale = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-  const float sy_scale = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-  const float sx = __fmul_rn(sx_scale, u), sy = __fmul_rn(sy_scale, v);
-  const int x0 = (int)sx, y0 = (int)sy;
-  const float lx = sx - (float)x0, ly = sy - (float)y0;
-  const int x1 = x0 + (x0 < w - 1 ? 1 : 0), y1 = y0 + (y0 < h - 1 ? 1 : 0);
+  const FeatureTaps t = feature_taps(q.u, q.v, h, w, H, W);
   const float* f = a.feat + (size_t)r * h * w * C;
-  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)y0 * w + x0) * C);
-  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)y0 * w + x1) * C);
-  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)y1 * w + x0) * C);
-  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)y1 * w + x1) * C);
-  for (uint32_t c = sub; c < C4; c += 16) {
-    const float4 t0 = f00[c], t1 = f01[c], t2 = f10[c], t3 = f11[c];
-    float4 o;
-    o.x = (1.f - ly) * ((1.f - lx) * t0.x + lx * t1.x) + ly * ((1.f - lx) * t2.x + lx * t3.x);
-    o.y = (1.f - ly) * ((1.f - lx) * t0.y + lx * t1.y) + ly * ((1.f - lx) * t2.y + lx * t3.y);
-    o.z = (1.f - ly) * ((1.f - lx) * t0.z + lx * t1.z) + ly * ((1.f - lx) * t2.z + lx * t3.z);
-    o.w = (1.f - ly) * ((1.f - lx) * t0.w + lx * t1.w) + ly * ((1.f - lx) * t2.w + lx * t3.w);
-    out[c] = o;
-  }
+  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x0) * C);
+  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x1) * C);
+  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x0) * C);
+  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x1) * C);
+  feature_row<16>(f00, f01, f10, f11, t.lx, t.ly, C4, sub, out);
 }
 
 // rel = p - o_r (fp32, utils/common.py:675), normalised with the bound in fp64 (dev_encode.hpp load_point's expression)

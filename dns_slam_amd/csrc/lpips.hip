@@ -14,7 +14,8 @@
 //                  float64 (the quotient as a product with the reciprocal), a wave per pixel; one float64 partial per workgroup,
 //                  added in a fixed order.
 // lpips_finish_kernel  adds the partials of each layer in index order, divides by h w, adds the layers.
-// All geometry is conv_plan.hpp's (checked on the host by tools/conv_plan_check.cpp).
+// All geometry is conv_plan.hpp's (checked on the host by tools/conv_plan_check.cpp); f32x16 and the NaN-keeping relu come
+// through it from conv_tile.hpp.
 #include "common.hpp"
 #include "conv_plan.hpp"
 
@@ -22,11 +23,8 @@ namespace dns {
 namespace {
 using namespace convp;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));      // (arrays of HIP's float4 class kept across the chunk loop end up in scratch)
 
-// ReLU that keeps a NaN (IEEE 754-2019 maximum; fmaxf returns 0 for a NaN), as in stem.hip
-__device__ __forceinline__ float relu(float a) { return __builtin_elementwise_maximum(a, 0.f); }
 // max that keeps a NaN of either side
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
 

@@ -9,6 +9,7 @@
 // the caller), and the per-point mean.  No atomics anywhere: a point's latents are added in list order, which is the
 // reference's keyframe order, so every result is the same bits from call to call and for every chunking by points.
 #include "common.hpp"
+#include "dev_feature.hpp"
 #include "dev_project.hpp"
 
 namespace dns {
@@ -61,9 +62,9 @@ __global__ __launch_bounds__(KFP_BLOCK) void kf_pair_kernel(const float* __restr
 
 // 16 lanes per pair, one float4 of channels per lane (feature_gather4_kernel's layout, feature.hip): rel[pair] = p - o_k and
 // the bilinear value of the half-resolution channels-last stem map [K, h, w, C] at the integer full-resolution pixel (iu, iv)
-// -- F.interpolate(align_corners=True) read at that pixel, the tap expressions of feature.hip:153-171 -- written at a row stride.
-// One addition to those expressions: x0 / y0 are clamped to the map (a bound on the tap addresses; sx <= w - 1 for every pixel
-// inside the image, so no value changes).
+// -- F.interpolate(align_corners=True) read at that pixel: feature_taps and feature_row of dev_feature.hpp -- written at a row
+// stride.  The pixel comes from a record, not from feature_project's inside test, so the taps are taken with CLAMP: x0 / y0 held
+// to the map (a bound on the tap addresses; sx <= w - 1 for every pixel inside the image, so no value changes).
 __global__ __launch_bounds__(256) void kf_pair_rows_kernel(const int4* __restrict__ rec, uint64_t n, const float* __restrict__ pts,
                                                            uint32_t P, const float* __restrict__ origin, uint32_t K,
                                                            const float* __restrict__ feat, uint32_t C, int h, int w, int H, int W,
@@ -74,29 +75,13 @@ __global__ __launch_bounds__(256) void kf_pair_rows_kernel(const int4* __restric
   const int4 r = rec[pair];
   if ((uint32_t)r.x >= P || (uint32_t)r.y >= K || (uint32_t)r.z >= (uint32_t)W || (uint32_t)r.w >= (uint32_t)H) return;
   if (sub < 3u) rel_out[pair * 3 + sub] = pts[(size_t)r.x * 3 + sub] - origin[(size_t)r.y * 3 + sub];
-  const float u = (float)r.z, v = (float)r.w;
-  const float sx_scale = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-  const float sy_scale = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-  const float sx = __fmul_rn(sx_scale, u), sy = __fmul_rn(sy_scale, v);
-  const int x0 = min((int)sx, w - 1), y0 = min((int)sy, h - 1);
-  const float lx = sx - (float)x0, ly = sy - (float)y0;
-  const int x1 = x0 + (x0 < w - 1 ? 1 : 0), y1 = y0 + (y0 < h - 1 ? 1 : 0);
+  const FeatureTaps t = feature_taps<true>((float)r.z, (float)r.w, h, w, H, W);
   const float* f = feat + (size_t)r.y * h * w * C;
-  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)y0 * w + x0) * C);
-  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)y0 * w + x1) * C);
-  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)y1 * w + x0) * C);
-  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)y1 * w + x1) * C);
-  float4* out = reinterpret_cast<float4*>(code + pair * ld_code);
-  const uint32_t C4 = C / 4u;
-  for (uint32_t c = sub; c < C4; c += 16) {
-    const float4 a = f00[c], b = f01[c], d = f10[c], e = f11[c];
-    float4 o;
-    o.x = (1.f - ly) * ((1.f - lx) * a.x + lx * b.x) + ly * ((1.f - lx) * d.x + lx * e.x);
-    o.y = (1.f - ly) * ((1.f - lx) * a.y + lx * b.y) + ly * ((1.f - lx) * d.y + lx * e.y);
-    o.z = (1.f - ly) * ((1.f - lx) * a.z + lx * b.z) + ly * ((1.f - lx) * d.z + lx * e.z);
-    o.w = (1.f - ly) * ((1.f - lx) * a.w + lx * b.w) + ly * ((1.f - lx) * d.w + lx * e.w);
-    out[c] = o;
-  }
+  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x0) * C);
+  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x1) * C);
+  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x0) * C);
+  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x1) * C);
+  feature_row<16>(f00, f01, f10, f11, t.lx, t.ly, C / 4u, sub, reinterpret_cast<float4*>(code + pair * ld_code));
 }
 
 // 8 lanes per point, one float4 of channels per lane and step: the point's segment of latents added in list order (the order

@@ -5,7 +5,8 @@
 // depend on its batch, its position or the call): M = 32 output pixels of one row, N = 2 x 32 channels, K = (ky, kx, c) padded
 // 147 -> 148.  A workgroup of 4 waves owns 8 rows x 32 pixels; its input tile with the halo (21 x 69 x 3 floats) and the packed
 // [148][64] weight image sit in LDS (55 KB: two workgroups per CU); a wave holds 2 rows x 64 channels in 64 accumulator registers.
-// All geometry is stem_tile.hpp's (checked on the host by tools/stem_tile_check.cpp).  A store instruction writes, per half wave,
+// All geometry is stem_tile.hpp's (checked on the host by tools/stem_tile_check.cpp); f32x16 and the NaN-keeping relu come
+// through it from conv_tile.hpp.  A store instruction writes, per half wave,
 // the 32 consecutive channels of one pixel: two whole 128-byte lines.  No atomics.
 //
 // Batch statistics (nn.BatchNorm2d in train mode, which is what the reference's never-eval()-ed stem computes): the forward kernel
@@ -18,11 +19,6 @@
 namespace dns {
 namespace {
 using namespace stem;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// ReLU that keeps a NaN (IEEE 754-2019 maximum; fmaxf returns 0 for a NaN), as in the MLP kernels
-__device__ __forceinline__ float relu(float a) { return __builtin_elementwise_maximum(a, 0.f); }
 
 template <bool STATS, bool EPI, bool STORE>
 __global__ __launch_bounds__(THREADS, 2) void stem_fwd_kernel(const float* __restrict__ images, int H, int W,

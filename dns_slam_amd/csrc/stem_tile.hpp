@@ -10,6 +10,7 @@
 // (0 * NaN would not be 0).
 #pragma once
 #include <stdint.h>
+#include "conv_tile.hpp"
 
 #if defined(__HIPCC__)
 #define DNS_STEM_HD __host__ __device__ inline
@@ -25,11 +26,12 @@ constexpr int K_REAL = KH * KW * CIN;              // 147
 constexpr int K_PAD = 148;                         // two k per matrix instruction
 constexpr int K_ROW = KW * CIN;                    // 21 consecutive floats of an input row per kernel row
 
-constexpr int THREADS = 256;                       // 4 waves
-constexpr int WAVES = 4;
-constexpr int TILE_W = 32;                         // output pixels of one matrix tile (M = 32) along x
-constexpr int ROWS_PER_WAVE = 2;                   // matrix tiles per wave: consecutive output rows
-constexpr int TILE_H = WAVES * ROWS_PER_WAVE;      // 8 output rows per workgroup
+// the workgroup shape and the accumulator map: conv_tile.hpp's, shared with the general convolution (conv_plan.hpp)
+using convt::THREADS; using convt::WAVES; using convt::TILE_W; using convt::ROWS_PER_WAVE; using convt::TILE_H;
+using convt::row_of; using convt::acc_pixel; using convt::acc_channel;
+#if defined(__HIPCC__)
+using convt::f32x16; using convt::relu;
+#endif
 
 constexpr int IN_ROWS = STRIDE * (TILE_H - 1) + KH;        // 21 input rows, halo included
 constexpr int IN_COLS = STRIDE * (TILE_W - 1) + KW;        // 69 input columns
@@ -104,12 +106,6 @@ DNS_STEM_HD void k_tap(int k, int* ky, int* kx, int* c) {
   *kx = (k % K_ROW) / CIN;
   *c = k % CIN;
 }
-
-// Accumulator element -> output: wave `wave`'s matrix tile `mt` is the tile's output row row_of(wave, mt); register r of lane l holds
-// the pixel acc_pixel(r, l) of that row and the channel acc_channel(l) (+ 32 for the second N block): the C/D map of the 32x32 forms
-DNS_STEM_HD int row_of(int wave, int mt) { return wave * ROWS_PER_WAVE + mt; }
-DNS_STEM_HD int acc_pixel(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-DNS_STEM_HD int acc_channel(int lane) { return lane & 31; }
 
 }  // namespace stem
 }  // namespace dns

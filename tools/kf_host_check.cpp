@@ -5,11 +5,12 @@
 // ascending keyframes and never on a depth hole, the bilinear value against float64, C = 6 refused, the mean bit-equal to the
 // ordered sum.  No GPU is involved.  From the repository root:
 //
-//   mkdir -p /tmp/kf_check && for f in dev_project.hpp mesh_feature.hip; do \
+//   mkdir -p /tmp/kf_check && for f in dev_project.hpp dev_feature.hpp mesh_feature.hip; do \
 //     sed -e 's/#include "common.hpp"//' -e 's/extern "C" //' dns_slam_amd/csrc/$f > /tmp/kf_check/$f; done
 //   g++ -std=c++20 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread \
 //       -Wno-unused-value -I/tmp/kf_check tools/kf_host_check.cpp -o /tmp/kf_check/kf_host_check && /tmp/kf_check/kf_host_check
-// (dev_project.hpp is taken from the source tree the same way as the kernels: only its include of the HIP headers is dropped.)
+// (dev_project.hpp and dev_feature.hpp are taken from the source tree the same way as the kernels: only their include of the HIP
+// headers is dropped.)
 #include <algorithm>
 #include <barrier>
 #include <cmath>

@@ -24,7 +24,7 @@ ENTRY = {  # C-ABI entry point -> kernels it launches
     "dns_raw_bwd": ["raw_bwd_kernel"], "dns_lattice_points": ["lattice_points_kernel"],
     # ABI v9 (round 4)
     "dns_encode_fwd_split": ["encode_fwd_split_kernel"], "dns_feature_block_split": ["feature_block_split_kernel"],
-    "dns_mlp_dwin": ["mlp_dwin_kernel"], "dns_feature_gather_frames": ["feature_gather_frames_kernel"],
+    "dns_mlp_dwin": ["mlp_dwin_kernel"], "dns_feature_gather_frames": ["feature_gather4_kernel", "feature_gather_kernel"],
     "dns_merge_dy": ["merge_dy_kernel"], "dns_add_ref_sum": ["add_ref_sum_kernel"], "dns_refer_poses": ["refer_poses_kernel"],
     "dns_draw_finish": ["draw_finish_kernel"], "dns_loss_finalize": ["loss_finalize_kernel"],
     "dns_loss_rays": ["loss_point_sums_kernel", "loss_rays_fused_kernel"],
@@ -32,7 +32,7 @@ ENTRY = {  # C-ABI entry point -> kernels it launches
     # dword reads, so the doubled figure is an UPPER bound for these two)
     "dns_mlp_fwd_half": ["mlp_half_fwd_kernel"], "dns_mlp_bwd_half": ["mlp_half_bwd_kernel"],
 }
-GATHER = ("encode_fwd_kernel", "encode_fwd_split_kernel", "encode_bwd_kernel", "hashgrid_bwd_binned_kernel", "feature_gather_frames_kernel",
+GATHER = ("encode_fwd_kernel", "encode_fwd_split_kernel", "encode_bwd_kernel", "hashgrid_bwd_binned_kernel", "feature_gather4_kernel", "feature_gather_kernel",
           "hashgrid_bwd_pairbins_kernel", "hashgrid_bwd_pairlist_kernel")
 
 
