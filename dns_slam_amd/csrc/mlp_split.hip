@@ -9,10 +9,10 @@ namespace sp {
 unsigned long long* g_bwd_trace = nullptr;
 #endif
 
-template <int NN, int NL, int PREC, bool XS = false>
+template <int NN, int NL, int PREC, bool XS = false, bool TAIL = false>
 __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  mlp_fwd_body<NN, NL, PREC, XS>(a, blockIdx.x, lds);
+  mlp_fwd_body<NN, NL, PREC, XS, TAIL>(a, blockIdx.x, lds);
 }
 
 // =================================================================================================================
@@ -134,7 +134,9 @@ static bool set_fwd_attrs() {
   return hipFuncSetAttribute((const void*)mlp_fwd_kernel<NN, NL, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess &&
          hipFuncSetAttribute((const void*)mlp_fwd_kernel<NN, NL, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess &&
          hipFuncSetAttribute((const void*)mlp_fwd_kernel<NN, NL, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess &&
-         hipFuncSetAttribute((const void*)mlp_fwd_kernel<NN, NL, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess;
+         hipFuncSetAttribute((const void*)mlp_fwd_kernel<NN, NL, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mlp_fwd_kernel<NN, NL, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mlp_fwd_kernel<NN, NL, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess;
 }
 
 static int split_init_attrs() {
@@ -174,10 +176,17 @@ int launch_mlp_fwd_split(const float* x, uint32_t ldx, const float* x2, uint32_t
   if (tpb < 1) tpb = 1;
   a.tiles_per_block = tpb;
   const uint32_t blocks = (n_btiles + tpb - 1) / tpb;
+  // a lone last output column (n_out = 1, 33) runs on the vector ALU (mlp_split.hpp, "tail column"): the fp32-grade
+  // arithmetic, on fp32 rows and split rows alike (bit-identical results); the fp16-operand arithmetic keeps its instances
+  const bool tail = tail_shape(n_out) && !fp16_single;
 #define LAUNCH_FWD(NN, NL)                                                                                           \
   {                                                                                                                  \
     const size_t lds_bytes = FwdLds<NN, NL>::total(n_in, n_out, 4);                                                  \
-    if (xs) {                                                                                                        \
+    if (tail) {                                                                                                      \
+      const size_t lds_tail = FwdLds<NN, NL>::total_tail(n_in, n_out, 4);                                            \
+      if (xs) DNS_LAUNCH((mlp_fwd_kernel<NN, NL, 3, true, true>), dim3(blocks), dim3(256), lds_tail, st, a);         \
+      else DNS_LAUNCH((mlp_fwd_kernel<NN, NL, 3, false, true>), dim3(blocks), dim3(256), lds_tail, st, a);           \
+    } else if (xs) {                                                                                                 \
       if (fp16_single) DNS_LAUNCH((mlp_fwd_kernel<NN, NL, 1, true>), dim3(blocks), dim3(256), lds_bytes, st, a);     \
       else DNS_LAUNCH((mlp_fwd_kernel<NN, NL, 3, true>), dim3(blocks), dim3(256), lds_bytes, st, a);                 \
     } else if (fp16_single) DNS_LAUNCH((mlp_fwd_kernel<NN, NL, 1>), dim3(blocks), dim3(256), lds_bytes, st, a);      \
@@ -284,7 +293,8 @@ int launch_mlp_dwin(const float* x, uint32_t ldx, const float* x2, uint32_t ldx2
 }
 
 // ---- prepared weight images (dns_mlp_prepare): per weight set [forward image area | 16 B exponents | backward image area
-// (with the dX image) | 16 B exponents]
+// (with the dX image) | 16 B exponents]; with a lone last output column (tail_shape) each exponent block is followed by W_out's
+// last row as n_neurons fp32 values
 static uint32_t prepared_fwd_bytes(uint32_t n_in, uint32_t n_out, uint32_t nn, uint32_t nl) {
   using namespace sp;
   uint32_t b;
@@ -292,7 +302,7 @@ static uint32_t prepared_fwd_bytes(uint32_t n_in, uint32_t n_out, uint32_t nn, u
   else if (nn == 32) b = FwdLds<32, 2>::misc(n_in, n_out);
   else if (nl == 1) b = FwdLds<64, 1>::misc(n_in, n_out);
   else b = FwdLds<64, 2>::misc(n_in, n_out);
-  return b + 16u;
+  return b + 16u + (tail_shape(n_out) ? nn * 4u : 0u);          // image area | exponents | (n_out = 1, 33) W_out's last row in fp32
 }
 static uint32_t prepared_bwd_bytes(uint32_t n_in, uint32_t n_out, uint32_t nn, uint32_t nl) {
   using namespace sp;

@@ -618,6 +618,50 @@ __device__ __forceinline__ float tile_max(const f32x16 (&a)[NT]) {      // after
   return max_halves(m);                      // the point's other lane half
 }
 
+// ---- a lone output column on the vector ALU ("tail column": n_out = 32 MT + 1, MT in {0, 1}) ---------------------------
+// The 33rd output of the coarse / fine networks and the single output of the lattice branch cost a whole 32-row output tile on
+// the matrix pipe.  In the accumulator layout a lane holds 16 NT hidden values of ONE point, so the column is 16 NT FMAs per
+// lane and one exchange between the point's two lane halves.  W_out's last row is kept as NN plain fp32 values in LDS (behind
+// the waves' areas): no image, no exponent, no operand rounding, no dropped product term.
+inline __host__ __device__ bool tail_shape(uint32_t n_out) { return n_out <= 33u && (n_out & 31u) == 1u; }
+
+// the lane's 16 weights of hidden tile t: rows acc_row(r, h) = 4 consecutive rows per register group, 16-byte LDS reads
+__device__ __forceinline__ void tail_weights(float (&w)[16], const float* __restrict__ w_tail, uint32_t t, uint32_t lane) {
+  const float* src = w_tail + 32u * t + 4u * (lane >> 5);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float4 v = *reinterpret_cast<const float4*>(src + 8 * g);
+    w[4 * g] = v.x; w[4 * g + 1] = v.y; w[4 * g + 2] = v.z; w[4 * g + 3] = v.w;
+  }
+}
+
+// v[lane] + v[lane ^ 32], the same bits in both lanes (lower half + upper half in that order)
+__device__ __forceinline__ float sum_halves(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// sum over the point's hidden units of act * w_tail (act still carries the point's exponent: the caller undoes it).
+// Roundings on sum |a||b|: four independent chains (one per register group) of 4 NT terms -- one rounding per term --, two
+// levels to join them, one for the other lane half: 4 NT + 3, i.e. 11 x 2^-24 at NN = 64 (7 at NN = 32), against
+// 2 x 2^-22 (operands) + 2^-22 (dropped term) + (NN / 16 + 1) 2^-24 that tests/mlp_ref.py allows the matrix path.
+template <int NT>
+__device__ __forceinline__ float tail_dot(const f32x16 (&act)[NT], const float* __restrict__ w_tail, uint32_t lane) {
+  float p[4];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    float w[16];
+    tail_weights(w, w_tail, t, lane);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      p[g] = t == 0 ? act[0][4 * g] * w[4 * g] : fmaf(act[t][4 * g], w[4 * g], p[g]);
+#pragma unroll
+      for (int e = 1; e < 4; ++e) p[g] = fmaf(act[t][4 * g + e], w[4 * g + e], p[g]);
+    }
+  }
+  return sum_halves((p[0] + p[1]) + (p[2] + p[3]));
+}
+
 // out[t] = W[t-th 32 rows] * act, act = accumulator tiles scaled by 2^kf on conversion; image in the CHAIN map.
 // The A fragments of K-step s+1 are requested before step s's operand is converted, so their LDS latency hides under
 // the conversion and the matrix instructions instead of stalling every step (s_waitcnt lgkmcnt(0) in front of each group).
@@ -1031,6 +1075,9 @@ struct FwdLds {
   static __host__ __device__ uint32_t total(uint32_t n_in, uint32_t n_out, uint32_t nwaves) {
     return stage(n_in, n_out) + nwaves * FWD_WAVE_FLOATS * 4u;
   }
+  // tail-column kernels: W_out's last row as NN floats behind the waves' areas (the image area keeps its layout: a tail kernel
+  // leaves the column's output tile unused, so one prepared blob serves both forms)
+  static __host__ __device__ uint32_t total_tail(uint32_t n_in, uint32_t n_out, uint32_t nwaves) { return total(n_in, n_out, nwaves) + NN * 4u; }
 };
 
 
@@ -1086,13 +1133,15 @@ struct FwdArgs {
 // (a __device__ body so that the fused tracker iteration, track_fused.inc, can run it as one of its phases: vb = the workgroup's
 //  index in this launch's grid, lds = the workgroup's dynamic LDS; images_ready: the caller has built weight set 0's images in
 //  this LDS already (build_fwd_images + a barrier) and calls the body many times on them -- frame_codes.hip, once per tile)
-template <int NN, int NL, int PREC, bool XS = false>
+// TAIL: n_out = 32 mt + 1 (tail_shape): mt (0 or 1) output tiles on the matrix pipe, the last column on the vector ALU
+template <int NN, int NL, int PREC, bool XS = false, bool TAIL = false>
 __device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsigned char* lds, bool images_ready = false) {
   constexpr int NT = NN / 32;
   using L = FwdLds<NN, NL>;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t n_in = a.n_in, n_out = a.n_out;
-  const uint32_t ns0 = L::ns0(n_in), mt = L::mt(n_out);
+  const uint32_t ns0 = L::ns0(n_in), mt = TAIL ? (n_out - 1u) >> 5 : L::mt(n_out);
+  float* w_tail = reinterpret_cast<float*>(lds + L::total(n_in, n_out, 4));
   const uint32_t n_chunks = (n_in + 31u) / 32u;
   const uint32_t n_btiles = (a.n_slots + 127u) / 128u;
   const uint32_t bt0 = vb * a.tiles_per_block;
@@ -1142,9 +1191,15 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsi
       if (grp >= 0) {
         if (a.prep) {
           const unsigned char* src = a.prep + (size_t)grp * a.prep_stride;
-          images_copy_in(lds, src, L::misc(n_in, n_out), src + L::misc(n_in, n_out), wexp);
+          // (TAIL: the column's own output tile, the last of the area, is not read)
+          images_copy_in(lds, src, TAIL ? L::img_out(n_in) + mt * (NN / 16) * 2048u : L::misc(n_in, n_out), src + L::misc(n_in, n_out), wexp);
+          if (TAIL && threadIdx.x < (uint32_t)NN) w_tail[threadIdx.x] = reinterpret_cast<const float*>(src + L::misc(n_in, n_out) + 16u)[threadIdx.x];
         }
-        if (!a.prep) build_fwd_images<NN, NL>(lds, a.params + (size_t)grp * a.param_stride, n_in, n_out, a.n_in_w);
+        if (!a.prep) {
+          const float* pw = a.params + (size_t)grp * a.param_stride;
+          build_fwd_images<NN, NL>(lds, pw, n_in, n_out, a.n_in_w);
+          if (TAIL && threadIdx.x < (uint32_t)NN) w_tail[threadIdx.x] = pw[NN * a.n_in_w + (NL - 1) * NN * NN + (n_out - 1u) * NN + threadIdx.x];
+        }
       }
       cur_group = grp;
       __syncthreads();
@@ -1235,6 +1290,23 @@ __device__ __forceinline__ void mlp_fwd_body(const FwdArgs& a, uint32_t vb, unsi
       }
     }
     const f32x16(&hl)[NT] = (NL == 2) ? a1 : a0;
+    if constexpr (TAIL) {
+      // the tail column from the un-split fp32 activations (they hold 2^kc * value: undone exactly), one dword per point
+      const float yt = ldexpf(tail_dot<NT>(hl, w_tail, lane), -kc);
+      if (mt != 0u) {                                // uniform: columns 0 .. 31 on the matrix pipe
+        const int kf = scale_exp(tile_max<NT>(hl));
+        kc += kf + wexp[2];
+        f32x16 o[1];
+        layer_chain<PREC, 1, NT>(hl, pow2f(kf), img_out, lane, o);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[0][r] = ldexpf(o[0][r], -kc);
+        store_tile_rows_scalar_buf(r_y, yoff, 0, 32u, o[0], stg, lane);
+      }
+      const uint32_t ot = lane < 32u ? yoff[lane & 31u] + 4u * (n_out - 1u) : BUF_OOB;   // (a padding slot's offset stays out of range)
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(yt), r_y, (int)ot, 0, 0);
+      wave_lds_fence();                              // yoff is rewritten at the next tile's start
+      continue;
+    }
     const int kf = scale_exp(tile_max<NT>(hl));
     kc += kf + wexp[2];
     const float fo = pow2f(kf);
@@ -1342,6 +1414,39 @@ __device__ __forceinline__ void flush_tile(const f32x16& a, float* __restrict__ 
   __syncthreads();
 }
 
+// the same for a tail column's partial sums (mlp_split_bwd.inc: rows = 32 hidden units, lanes = the wave's 32 points): every
+// row is summed over the four waves' copies and their 32 point lanes, and the 32 sums go to dst[0 .. 31] in ONE atomic
+// instruction of 32 lanes (a 128-byte segment, as flush_tile's) -- every workgroup adds into the same NN floats, and an
+// instruction per row sum (first attempt: 32 single-lane atomics per tile and workgroup onto two cache lines) cost 27-30 us per
+// launch.  red32: 32 floats of LDS nobody else uses at flush time.  Roundings of one entry: one per tile of the run (the lane's
+// FMA), then a tree of seven levels (2 inside a float4, 2 over the waves, 3 over the row's eight threads).
+template <uint32_t WAVE_FLOATS = STG_WAVE_FLOATS>
+__device__ __forceinline__ void flush_tail(const f32x16& a, float* __restrict__ dst, float* __restrict__ stg_base, float* __restrict__ red32,
+                                           uint32_t wave, uint32_t lane) {
+  float* stg = stg_base + wave * WAVE_FLOATS;
+  const uint32_t j = lane & 31u, h = lane >> 5;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) stg[acc_row(r, h) * STG_LD + j] = a[r];
+  __syncthreads();
+  const uint32_t row = wave * 8u + (lane >> 3), c4 = 4u * (lane & 7u);   // 8 threads per row, 4 columns each
+  float sw[4];
+#pragma unroll
+  for (uint32_t w = 0; w < 4u; ++w) {
+    const float4 v = *reinterpret_cast<const float4*>(stg_base + w * WAVE_FLOATS + row * STG_LD + c4);
+    sw[w] = (v.x + v.y) + (v.z + v.w);
+  }
+  float v = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+  v += dpp_mov<0xB1>(v);                       // lane ^ 1
+  v += dpp_mov<0x4E>(v);                       // lane ^ 2
+  v += dpp_mov<0x141>(v);                      // row_half_mirror: the other quad of the row's 8 threads
+  if ((lane & 7u) == 0u) red32[row] = v;
+  __syncthreads();
+  if (threadIdx.x < 32u) {
+    const float t = red32[threadIdx.x];
+    if (t != 0.f) atomicAdd(dst + threadIdx.x, t);
+  }
+  __syncthreads();
+}
 
 }  // namespace sp
 }  // namespace dns

@@ -103,25 +103,37 @@ __global__ __launch_bounds__(256) void mlp_prepare_kernel(const float* __restric
     build_fwd_images<NN, NL>(lds, pw, n_in, n_out, n_in_w);
     __syncthreads();
     images_copy_out(lds, dst, LF::misc(n_in, n_out), reinterpret_cast<const int*>(lds + LF::misc(n_in, n_out)));
+    dst += LF::misc(n_in, n_out) + 16u;
   } else {
     using L = BwdLds<NCH, MT>;
     build_bwd_images<NCH, MT>(lds, pw, n_in, n_out, true, n_in_w);
     __syncthreads();
     images_copy_out(lds, dst + fwd_bytes, L::misc(true), reinterpret_cast<const int*>(lds + L::misc(true)));
+    dst += fwd_bytes + L::misc(true) + 16u;
   }
+  // a lone last output column (tail_shape): W_out's last row in fp32 behind the exponents, for the tail-column kernels
+  if (tail_shape(n_out) && threadIdx.x < (uint32_t)NN)
+    reinterpret_cast<float*>(dst)[threadIdx.x] = pw[NN * n_in_w + (NL - 1) * NN * NN + (n_out - 1u) * NN + threadIdx.x];
 }
 
 // SH: the hidden activations come from what the forward kept (a.h_saved) instead of being recomputed from x (phase A)
 // XS: x arrives in the split-row format (split_rows.hpp): phase A's operand fragments come straight from memory
 // (a __device__ body so that the fused tracker iteration, track_fused.inc, can run it as one of its phases: vb = the workgroup's
 //  index in this launch's grid, lds = the workgroup's dynamic LDS)
-template <int NCH, int MT, int PREC, bool WITH_DW, bool SH = false, bool XS = false, int NW = 4>
+// TAIL = 1: n_out = 32 MT + 1 (tail_shape; MT = 0 or 1).  MT output tiles run on the matrix pipe as before, the last column
+// ("tail column", mlp_split.hpp) on the vector ALU: its dY is one dword per point, its share of dH_last one FMA per hidden
+// unit on the fp32 accumulators, its row of dW_out 16 NT per-lane partial sums over the lane's points -- persistent like
+// acc_out (zeroed and flushed at the same two places), reduced over the 32 point lanes once per run.  The LDS image area and the
+// prepared blob keep the layout of the MT + 1 tiles the column used to cost; its tile of them is not read.
+template <int NCH, int MT, int PREC, bool WITH_DW, bool SH = false, bool XS = false, int NW = 4, int TAIL = 0>
 __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsigned char* lds) {
   static_assert(NW == 4 || !WITH_DW, "the weight-gradient reduction (flush_tile) is written for 4 waves");
+  static_assert(MT >= 1 || TAIL == 1, "no output column");
   constexpr uint32_t BT_SLOTS = 32u * NW;        // point slots per workgroup tile
   constexpr int NT = NN / 32;
-  constexpr uint32_t NS0 = 2 * NCH, NSO = 2 * MT;
-  using L = BwdLds<NCH, MT>;
+  constexpr int MA = MT > 0 ? MT : 1;            // array extents (MT = 0: the arrays are unused)
+  constexpr uint32_t NS0 = 2 * NCH, NSO = 2 * (MT + TAIL);     // (K-steps of the W_out^T image AS LAID OUT; 2 MT of them are run)
+  using L = BwdLds<NCH, MT + TAIL>;
   // the wave index as a SCALAR: everything derived from it (slot numbers, the staging tile's address) stays out of the vector
   // registers and the vector ALU
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -141,6 +153,8 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
   int* rows_all = reinterpret_cast<int*>(stg + STG_FLOATS);
   float* rmax = stg + STG_FLOATS + STG_ROWS;
   uint32_t* offs = reinterpret_cast<uint32_t*>(stg + STG_WAVE_FLOATS);   // the tile's row offsets in dy | d_x | d_x2 (bytes)
+  float* w_tail = reinterpret_cast<float*>(lds + L::total(need_dx, NW));  // (TAIL) 2^wexp[2] * W_out's last row, fp32 (exact)
+  const uint32_t n_out_mat = n_out - (uint32_t)TAIL;                       // output columns on the matrix pipe
   // buffer descriptors of everything the tile loop loads or stores behind a row / column guard (mlp_split.hpp)
   const rsrc_t r_dy = buf_make(a.dy), r_dh1 = buf_make(a.dh1), r_ri = buf_make(a.row_index);
   DxIo io;
@@ -173,7 +187,8 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
   };
 
   // weight-gradient accumulators of the wave (rows = dW rows in the 16 registers, lanes = dW columns)
-  f32x16 acc_out[WITH_DW ? MT : 1][WITH_DW ? NT : 1];     // [row tile of n_out][column tile of the hidden width]
+  f32x16 acc_out[WITH_DW ? MA : 1][WITH_DW ? NT : 1];     // [row tile of n_out][column tile of the hidden width]
+  f32x16 part[WITH_DW && TAIL ? NT : 1];                   // (TAIL) the lane's partial sums of dW_out's last row: dy_tail * H_last
   f32x16 acc_h[WITH_DW && NL == 2 ? NT : 1][WITH_DW && NL == 2 ? NT : 1];
   XChunk xc[(SH || XS) ? 1 : NCH];              // the tile's input chunks (recompute)
   XsTile xt;                                    // (XS) the tile's input fragments
@@ -221,8 +236,13 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
       // the FULL area in the blob
       const unsigned char* src = a.prep + (size_t)grp * a.prep_stride;
       images_copy_in(lds, src, L::misc(need_dx), src + L::misc(true), wexp);
+      if (TAIL && threadIdx.x < (uint32_t)NN)
+        w_tail[threadIdx.x] = ldexpf(reinterpret_cast<const float*>(src + L::misc(true) + 16u)[threadIdx.x], reinterpret_cast<const int*>(src + L::misc(true))[2]);
     } else {
-      build_bwd_images<NCH, MT>(lds, a.params + (size_t)grp * a.param_stride, n_in, n_out, need_dx, a.n_in_w);
+      const float* pw = a.params + (size_t)grp * a.param_stride;
+      build_bwd_images<NCH, MT + TAIL>(lds, pw, n_in, n_out, need_dx, a.n_in_w);     // (wexp is final behind the barrier of its block_scale_exps)
+      if (TAIL && threadIdx.x < (uint32_t)NN)
+        w_tail[threadIdx.x] = ldexpf(pw[NN * a.n_in_w + (NL - 1) * NN * NN + (n_out - 1u) * NN + threadIdx.x], wexp[2]);
     }
     __syncthreads();
     DNS_TR_RUN(1);
@@ -231,6 +251,10 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc_out[i][j] = zero16();
+      if constexpr (TAIL != 0) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) part[j] = zero16();
+      }
       if constexpr (NL == 2) {
 #pragma unroll
         for (int i = 0; i < NT; ++i)
@@ -246,9 +270,12 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
     if (bt + 1 < run1) row_next = row_fetch((bt + 1) * BT_SLOTS + wave * 32u);
     tile_offs_publish(offs, rows_lds, a.lddy, a.lddx, a.dseg.lddx2, row_limit, bad_rows, lane);
     // dY of the tile: requested now, used after the recompute
-    DyChunk dyc[MT];
+    DyChunk dyc[MA];
 #pragma unroll
-    for (int c = 0; c < MT; ++c) dy_chunk_issue_buf(dyc[c], r_dy, offs, n_out, c, lane);
+    for (int c = 0; c < MT; ++c) dy_chunk_issue_buf(dyc[c], r_dy, offs, n_out_mat, c, lane);
+    // (TAIL) the point's dY in the last column: one dword, the same in both lane halves; a padding slot reads zero
+    float dy_tail = 0.f;
+    if constexpr (TAIL != 0) dy_tail = buf_load1(r_dy, offs[lane & 31u] + 4u * (n_out - 1u));
 
     // ---- A: the hidden activations: recomputed from x, or (SH) read back as the forward kept them ----------------------
     int k0 = 0, k1 = 0;
@@ -316,9 +343,9 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
 
     DNS_TR(1);
     // ---- B: dH_last = W_out^T dY (.) relu' ----------------------------------------------------------------------
-    float dys[MT][16];
-    float dyt[WITH_DW ? MT : 1][16];           // the same tile column-wise (lane = output column): phase C's operand
-    float dymax = 0.f;
+    float dys[MA][16];
+    float dyt[WITH_DW ? MA : 1][16];           // the same tile column-wise (lane = output column): phase C's operand
+    float dymax = fabsf(dy_tail);              // (0 without a tail column)
 #pragma unroll
     for (int c = 0; c < MT; ++c) {
       dy_chunk_commit(dyc[c], stg, lane);
@@ -348,6 +375,18 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
       }
     }
     const int kdl = kdy + wexp[2];            // dl holds 2^kdl * dH_last
+    if constexpr (TAIL != 0) {
+      // the tail column's share, at dl's exponent: (2^wexp[2] w)(2^kdy dy) -- both factors exact (below 2^14 in magnitude, as
+      // the matrix operands are; the row is kept scaled in LDS), one rounding for the FMA
+      const float dts = dy_tail * pow2f(kdy);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        float w[16];
+        tail_weights(w, w_tail, t, lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dl[t][r] = fmaf(w[r], dts, dl[t][r]);
+      }
+    }
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -355,10 +394,18 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
 
     DNS_TR(2);
     // ---- C: dW_out += dY x H_last (sum over the tile's points) ---------------------------------------------------
-    if constexpr (WITH_DW) {
+    if constexpr (WITH_DW && TAIL != 0) {
+      // the tail column's row of dW_out: the lane's point contributes dy_tail * H_last to its 16 NT hidden units (true scale:
+      // the exponent of hl is undone exactly); one FMA rounding per tile, the cross-lane sum waits for the end of the run
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[t][r] = fmaf(dy_tail, ldexpf(hl[t][r], -khl), part[t][r]);
+    }
+    if constexpr (WITH_DW && MT > 0) {
       // dY^T-form: lane = output column, elements = 8 consecutive points -- taken from the staged tile in phase B (round 2
       // first re-read it from L1 as dwords here: a full memory latency exposed per tile at one wave per SIMD)
-      Frag3 fa[MT][2];
+      Frag3 fa[MA][2];
 #pragma unroll
       for (int c = 0; c < MT; ++c)
 #pragma unroll
@@ -542,8 +589,13 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j)
-            flush_tile<BWD_WAVE_FLOATS>(acc_out[i][j], dW_out + (size_t)(32 * i) * NN + 32 * j, NN, n_out > 32u * i ? n_out - 32u * i : 0u, 32u,
+            flush_tile<BWD_WAVE_FLOATS>(acc_out[i][j], dW_out + (size_t)(32 * i) * NN + 32 * j, NN, n_out_mat > 32u * i ? n_out_mat - 32u * i : 0u, 32u,
                        stg_base, wave, lane);
+        if constexpr (TAIL != 0) {
+#pragma unroll
+          for (int j = 0; j < NT; ++j)
+            flush_tail<BWD_WAVE_FLOATS>(part[j], dW_out + (size_t)(n_out - 1u) * NN + 32 * j, stg_base, stg_base + STG_FLOATS + STG_ROWS, wave, lane);
+        }
       }
     }
     DNS_TR_RUN(3);
@@ -552,39 +604,50 @@ __device__ __forceinline__ void mlp_bwd_body(const BwdArgs& a, uint32_t vb, unsi
   if (bad_rows != 0u && a.err) atomicOr(a.err, DNS_DEVERR_MLP_RANGE);
 }
 
-template <int NCH, int MT, int PREC, bool WITH_DW, bool SH = false, bool XS = false, int NW = 4>
+template <int NCH, int MT, int PREC, bool WITH_DW, bool SH = false, bool XS = false, int NW = 4, int TAIL = 0>
 __global__ __launch_bounds__(64 * NW, 1) void mlp_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  mlp_bwd_body<NCH, MT, PREC, WITH_DW, SH, XS, NW>(a, blockIdx.x, lds);
+  mlp_bwd_body<NCH, MT, PREC, WITH_DW, SH, XS, NW, TAIL>(a, blockIdx.x, lds);
 }
 
 #if defined(DNS_BWD_DEV_ONE)
 // tools build (hipcc -S of ONE instance in seconds instead of the file's 78: tools/isa_one.sh): nothing else is instantiated
 template __global__ void mlp_bwd_kernel<DNS_BWD_DEV_ONE>(BwdArgs);
 #elif !defined(DNS_BWD_BODY_ONLY)            // (BODY_ONLY: track_fused.inc wants BwdLds + mlp_bwd_body, no launchers)
-template <int NCH, int MT>
+template <int NCH, int MT, int TAIL>
 bool set_attrs() {
   bool ok = true;
   auto set = [&](const void* f) { ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess; };
-  set((const void*)mlp_bwd_kernel<NCH, MT, 3, true>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 1, true>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 1, false>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 3, true, true>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 3, true, false, true>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false, false, true>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 1, true, false, true>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 1, false, false, true>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false, false, false, 8>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 1, false, false, false, 8>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false, false, true, 8>);
-  set((const void*)mlp_bwd_kernel<NCH, MT, 1, false, false, true, 8>);
-  set((const void*)mlp_prepare_kernel<NCH, MT>);
+  set((const void*)mlp_bwd_kernel<NCH, MT, 3, true, false, false, 4, TAIL>);
+  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false, false, false, 4, TAIL>);
+  set((const void*)mlp_bwd_kernel<NCH, MT, 3, true, true, false, 4, TAIL>);
+  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false, false, false, 8, TAIL>);
+  set((const void*)mlp_bwd_kernel<NCH, MT, 3, true, false, true, 4, TAIL>);
+  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false, false, true, 4, TAIL>);
+  set((const void*)mlp_bwd_kernel<NCH, MT, 3, false, false, true, 8, TAIL>);
+  if constexpr (TAIL == 0) {                     // the fp16-operand arithmetic and the image builder have no tail-column form
+    set((const void*)mlp_bwd_kernel<NCH, MT, 1, true>);
+    set((const void*)mlp_bwd_kernel<NCH, MT, 1, false>);
+    set((const void*)mlp_bwd_kernel<NCH, MT, 1, true, false, true>);
+    set((const void*)mlp_bwd_kernel<NCH, MT, 1, false, false, true>);
+    set((const void*)mlp_bwd_kernel<NCH, MT, 1, false, false, false, 8>);
+    set((const void*)mlp_bwd_kernel<NCH, MT, 1, false, false, true, 8>);
+    set((const void*)mlp_prepare_kernel<NCH, MT>);
+  }
+  return ok;
+}
+
+// (tail-column instances exist for up to 96 input columns: with four input chunks the <4, 1, TAIL> weight-gradient instance
+//  spills 54 registers where <4, 2> spills 2, and no network of the project has that shape)
+template <int NCH>
+bool set_attrs_nch() {
+  bool ok = set_attrs<NCH, 1, 0>() && set_attrs<NCH, 2, 0>();
+  if constexpr (NCH < 4) ok = ok && set_attrs<NCH, 0, 1>() && set_attrs<NCH, 1, 1>();
   return ok;
 }
 
 int init_attrs() {
-  const bool ok = set_attrs<1, 1>() && set_attrs<1, 2>() && set_attrs<3, 1>() && set_attrs<3, 2>() && set_attrs<4, 1>() && set_attrs<4, 2>();
+  const bool ok = set_attrs_nch<1>() && set_attrs_nch<3>() && set_attrs_nch<4>();
   if (!ok) {
     set_error("dns_init: hipFuncSetAttribute failed for the MLP backward kernels");
     return DNS_E_LAUNCH;
@@ -593,39 +656,47 @@ int init_attrs() {
 }
 AttrRegistrar attr_registrar(init_attrs);
 
-template <int NCH, int MT>
+// TAIL = 1 (fp32-grade arithmetic only): the LDS of the MT + 1 tile layout plus W_out's last row
+template <int NCH, int MT, int TAIL = 0>
 void launch(const BwdArgs& a, uint32_t blocks, bool fp16_single, hipStream_t st) {
   const bool xs = a.xs.s1.rows != nullptr;
+  constexpr size_t tail_bytes = TAIL ? NN * 4u : 0u;
+#define DNS_BWD_GO(PREC_, DW_, SH_, XS_, NW_, lds_)                                                                             \
+  {                                                                                                                             \
+    if constexpr (TAIL == 0 || PREC_ == 3)                                                                                      \
+      DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, PREC_, DW_, SH_, XS_, NW_, TAIL>), dim3(blocks), dim3(64 * NW_), lds_, st, a);       \
+  }
   if (a.n_waves == 8u) {                         // frozen-scene form, two waves per SIMD (mlp_split.hip picks it: no d_params, no groups)
-    const size_t lds8 = BwdLds<NCH, MT>::total(a.dx != nullptr, 8u);
+    const size_t lds8 = BwdLds<NCH, MT + TAIL>::total(a.dx != nullptr, 8u) + tail_bytes;
     if (xs) {
-      if (fp16_single) DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 1, false, false, true, 8>), dim3(blocks), dim3(512), lds8, st, a);
-      else DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 3, false, false, true, 8>), dim3(blocks), dim3(512), lds8, st, a);
+      if (fp16_single) DNS_BWD_GO(1, false, false, true, 8, lds8)
+      else DNS_BWD_GO(3, false, false, true, 8, lds8)
     } else {
-      if (fp16_single) DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 1, false, false, false, 8>), dim3(blocks), dim3(512), lds8, st, a);
-      else DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 3, false, false, false, 8>), dim3(blocks), dim3(512), lds8, st, a);
+      if (fp16_single) DNS_BWD_GO(1, false, false, false, 8, lds8)
+      else DNS_BWD_GO(3, false, false, false, 8, lds8)
     }
     return;
   }
-  const size_t lds_bytes = BwdLds<NCH, MT>::total(a.dx != nullptr, 4u);
+  const size_t lds_bytes = BwdLds<NCH, MT + TAIL>::total(a.dx != nullptr, 4u) + tail_bytes;
   if (xs) {
     if (a.d_params) {
-      if (fp16_single) DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 1, true, false, true>), dim3(blocks), dim3(256), lds_bytes, st, a);
-      else DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 3, true, false, true>), dim3(blocks), dim3(256), lds_bytes, st, a);
+      if (fp16_single) DNS_BWD_GO(1, true, false, true, 4, lds_bytes)
+      else DNS_BWD_GO(3, true, false, true, 4, lds_bytes)
     } else {
-      if (fp16_single) DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 1, false, false, true>), dim3(blocks), dim3(256), lds_bytes, st, a);
-      else DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 3, false, false, true>), dim3(blocks), dim3(256), lds_bytes, st, a);
+      if (fp16_single) DNS_BWD_GO(1, false, false, true, 4, lds_bytes)
+      else DNS_BWD_GO(3, false, false, true, 4, lds_bytes)
     }
     return;
   }
   if (a.d_params) {
-    if (fp16_single) DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 1, true>), dim3(blocks), dim3(256), lds_bytes, st, a);
-    else if (a.h_saved) DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 3, true, true>), dim3(blocks), dim3(256), lds_bytes, st, a);
-    else DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 3, true>), dim3(blocks), dim3(256), lds_bytes, st, a);
+    if (fp16_single) DNS_BWD_GO(1, true, false, false, 4, lds_bytes)
+    else if (a.h_saved) DNS_BWD_GO(3, true, true, false, 4, lds_bytes)
+    else DNS_BWD_GO(3, true, false, false, 4, lds_bytes)
   } else {
-    if (fp16_single) DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 1, false>), dim3(blocks), dim3(256), lds_bytes, st, a);
-    else DNS_LAUNCH((mlp_bwd_kernel<NCH, MT, 3, false>), dim3(blocks), dim3(256), lds_bytes, st, a);
+    if (fp16_single) DNS_BWD_GO(1, false, false, false, 4, lds_bytes)
+    else DNS_BWD_GO(3, false, false, false, 4, lds_bytes)
   }
+#undef DNS_BWD_GO
 }
 
 #endif  // DNS_BWD_DEV_ONE / DNS_BWD_BODY_ONLY
@@ -636,16 +707,22 @@ void launch(const BwdArgs& a, uint32_t blocks, bool fp16_single, hipStream_t st)
 #define DNS_LAUNCH_NAME(nn, nl) DNS_CAT3(launch_bwd_, nn, nl)
 int DNS_LAUNCH_NAME(DNS_BWD_NN, DNS_BWD_NL)(const BwdArgs& a, uint32_t blocks, bool fp16_single, hipStream_t st) {
   const uint32_t nch = a.n_in <= 32u ? 1u : (a.n_in <= 96u ? 3u : 4u), mt = a.n_out <= 32u ? 1u : 2u;
-  if (nch == 1u) {
-    if (mt == 1u) launch<1, 1>(a, blocks, fp16_single, st);
-    else launch<1, 2>(a, blocks, fp16_single, st);
-  } else if (nch == 3u) {
-    if (mt == 1u) launch<3, 1>(a, blocks, fp16_single, st);
-    else launch<3, 2>(a, blocks, fp16_single, st);
-  } else {
-    if (mt == 1u) launch<4, 1>(a, blocks, fp16_single, st);
-    else launch<4, 2>(a, blocks, fp16_single, st);
+  // a lone last output column (n_out = 1, 33) runs on the vector ALU: one matrix tile less (DESIGN 4.22).  fp32 rows and split
+  // rows alike (their results are bit-identical: tests/test_gpu_split_rows.py); the fp16-operand arithmetic and n_in > 96 keep
+  // their instances
+  const bool tail = tail_shape(a.n_out) && !fp16_single && nch != 4u;
+#define DNS_BWD_PICK(NCH_)                                          \
+  {                                                                 \
+    if (tail && mt == 1u) launch<NCH_, 0, 1>(a, blocks, false, st);  \
+    else if (tail) launch<NCH_, 1, 1>(a, blocks, false, st);         \
+    else if (mt == 1u) launch<NCH_, 1>(a, blocks, fp16_single, st);  \
+    else launch<NCH_, 2>(a, blocks, fp16_single, st);                \
   }
+  if (nch == 1u) DNS_BWD_PICK(1)
+  else if (nch == 3u) DNS_BWD_PICK(3)
+  else if (mt == 1u) launch<4, 1>(a, blocks, fp16_single, st);
+  else launch<4, 2>(a, blocks, fp16_single, st);
+#undef DNS_BWD_PICK
   return check_launch("dns_mlp_bwd");
 }
 
@@ -658,7 +735,7 @@ uint32_t DNS_PREPB_NAME(DNS_BWD_NN, DNS_BWD_NL)(uint32_t n_in, uint32_t n_out) {
   if (nch == 1u) b = mt == 1u ? BwdLds<1, 1>::misc(true) : BwdLds<1, 2>::misc(true);
   else if (nch == 3u) b = mt == 1u ? BwdLds<3, 1>::misc(true) : BwdLds<3, 2>::misc(true);
   else b = mt == 1u ? BwdLds<4, 1>::misc(true) : BwdLds<4, 2>::misc(true);
-  return b + 16u;
+  return b + 16u + (tail_shape(n_out) ? NN * 4u : 0u);
 }
 int DNS_PREP_NAME(DNS_BWD_NN, DNS_BWD_NL)(const float* params, uint32_t param_stride, uint32_t n_in, uint32_t n_out, uint32_t n_sets,
                                           unsigned char* blob, uint32_t fwd_bytes, uint32_t blob_stride, hipStream_t st, uint32_t n_in_w) {
