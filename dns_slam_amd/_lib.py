@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class DnsGridMeta(C.Structure):
@@ -53,7 +53,11 @@ class DnsTrackFused(C.Structure):
                 ("lambda_p", C.c_float), ("lambda_d", C.c_float), ("lambda_l", C.c_float),
                 ("ws", _P), ("adam_m", _P), ("adam_v", _P), ("adam_state", _P),
                 ("lr_quat", C.c_float), ("lr_trans", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
-                ("best_loss", _P), ("best_cam", _P), ("out", _P), ("g_quat", _P), ("g_trans", _P)]
+                ("best_loss", _P), ("best_cam", _P), ("out", _P), ("g_quat", _P), ("g_trans", _P),
+                # the stem form (ABI v25): maps != NULL = the 2-D branch of a stem-trained map inside the iteration
+                ("maps", _P), ("w2c", _P), ("origin", _P), ("follow_mask", _U), ("w_merge", _P),
+                ("merge_in", _U), ("merge_out", _U), ("merge_bins", _U), ("merge_bound", _P),
+                ("n_views", _U), ("map_c", _U), ("map_h", C.c_int32), ("map_w", C.c_int32)]
 
 # name -> (restype, argtypes); must list every symbol include/dns_hip.h declares (tests/test_abi.py checks)
 SIGNATURES = {
@@ -106,6 +110,7 @@ SIGNATURES = {
     "dns_track_mask": (C.c_int, [_P, _P, _U, C.c_float, _P, _P]),
     "dns_keep_best": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "dns_force_half": (C.c_int, [_P, _U, _U, _P]),
+    "dns_track_fused_args_bytes": (C.c_uint64, []),
     "dns_track_fused_ws_floats": (C.c_uint64, [C.POINTER(DnsTrackFused)]),
     "dns_track_fused_begin": (C.c_int, [_P, _U, _U, _P, _I, _I, _I, _I, _P, _U, _P, _P]),
     "dns_track_fused_iter": (C.c_int, [C.POINTER(DnsTrackFused), _P]),

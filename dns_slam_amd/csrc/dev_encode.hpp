@@ -8,6 +8,7 @@
 // Row arguments are a template parameter (RowP): the tracker passes explicit LDS address-space pointers (track_fused.inc, lds_fp).
 #pragma once
 #include "common.hpp"
+#include "dev_rn.hpp"
 
 namespace dns {
 
@@ -40,7 +41,7 @@ __device__ __forceinline__ void grid_cell(const float x[3], float s, uint32_t g[
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     const int a = X_FIRST ? i : 2 - i;
-    const float pos = __fadd_rn(__fmul_rn(x[a], s), 0.5f);
+    const float pos = DNS_FADD(DNS_FMUL(x[a], s), 0.5f);         // (dev_rn.hpp)
     const float fl = floorf(pos);
     g[a] = (uint32_t)(int)fl;
     f[a] = pos - fl;

@@ -68,4 +68,71 @@ __device__ __forceinline__ void feature_row(const V* f00, const V* f01, const V*
     out[c] = feature_blend(lx, ly, a, b, d, e);
   }
 }
+
+// ---- a (point, view) pair of the in-kernel 2-D branch: frame_codes.hip (phase A) and track_fused.inc (phase 3a) -----------------
+// The pair's code -> dst[0 .. C) (16-byte aligned, C % 4 == 0), lane `sub` of the pair's 16: what feature_gather4_kernel does.
+// m: the view's w2c (its first 12 floats are read), f: the view's map [h, w, C].  Not valid, or not kept: zeros, and no tap is read.
+__device__ __forceinline__ void pair_code(const float* m, const Mat3& K, const float* __restrict__ f, uint32_t C, int h, int w, int H,
+                                          int W, float x, float y, float z, bool kept, uint32_t sub, float* __restrict__ dst) {
+  const FeaturePixel q = feature_project(m, K, x, y, z, H, W, kept);
+  const uint32_t C4 = C / 4u;
+  float4* out = reinterpret_cast<float4*>(dst);
+  if (!q.ok) {
+    for (uint32_t c = sub; c < C4; c += 16) out[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const FeatureTaps t = feature_taps(q.u, q.v, h, w, H, W);
+  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x0) * C);
+  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x1) * C);
+  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x0) * C);
+  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x1) * C);
+  feature_row<16>(f00, f01, f10, f11, t.lx, t.ly, C4, sub, out);
+}
+// rel = p - o_r (fp32, utils/common.py:675), normalised with Merge's bound in fp64 (dev_encode.hpp load_point's expression)
+__device__ __forceinline__ void pair_rel(const float (&p)[3], const float (&o)[3], const double (&b0)[3], const double (&b1)[3],
+                                         float (&x)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float rel = p[k] - o[k];
+    x[k] = (float)(((double)rel - b0[k]) / (b1[k] - b0[k]));
+  }
+}
+
+// ---- a reference view's pose -> w2c and origin: refer_poses_kernel (feature.hip) and the fused tracker's following views --------
+// Rotation of the quaternion AS IT STANDS IN THE OPTIMISER (get_rotation_from_quad, utils/common.py:406-429: two_s = 2 / |q|^2, no
+// normalisation) and the translation, as float64 A [3 x 3], t [3]
+__device__ __forceinline__ void pose_from_quat(const float* q, const float* trans, double (&A)[9], double (&t)[3]) {
+#pragma clang fp contract(off)
+  const float qw = q[0], qx = q[1], qy = q[2], qz = q[3];
+  const float two_s = 2.0f / (qw * qw + qx * qx + qy * qy + qz * qz);
+  const float Rm[9] = {1.0f - two_s * (qy * qy + qz * qz), two_s * (qx * qy - qz * qw), two_s * (qx * qz + qy * qw),
+                       two_s * (qx * qy + qz * qw), 1.0f - two_s * (qx * qx + qz * qz), two_s * (qy * qz - qx * qw),
+                       two_s * (qx * qz - qy * qw), two_s * (qy * qz + qx * qw), 1.0f - two_s * (qx * qx + qy * qy)};
+#pragma unroll
+  for (int i = 0; i < 9; ++i) A[i] = (double)Rm[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = (double)trans[i];
+}
+// w2c = the affine inverse of [A | t] (the 3 x 3 block inverted by cofactors in float64; torch.inverse in the reference), rows
+// 0..2 -> o[0 .. 12), the last row -> o[12 .. 16) unless ROWS3; origin = t (refer_o, utils/common.py:674)
+template <bool ROWS3 = false, typename OutP>
+__device__ __forceinline__ void pose_inverse(const double (&A)[9], const double (&t)[3], OutP o, OutP origin) {
+#pragma clang fp contract(off)
+  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
+  const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
+  const double id = 1.0 / det;
+  const double I[9] = {c00 * id, (A[2] * A[7] - A[1] * A[8]) * id, (A[1] * A[5] - A[2] * A[4]) * id,
+                       c01 * id, (A[0] * A[8] - A[2] * A[6]) * id, (A[2] * A[3] - A[0] * A[5]) * id,
+                       c02 * id, (A[1] * A[6] - A[0] * A[7]) * id, (A[0] * A[4] - A[1] * A[3]) * id};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[4 * i + j] = (float)I[3 * i + j];
+    o[4 * i + 3] = (float)(-(I[3 * i] * t[0] + I[3 * i + 1] * t[1] + I[3 * i + 2] * t[2]));
+  }
+  if (!ROWS3) { o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f; }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) origin[i] = (float)t[i];
+}
 }  // namespace dns

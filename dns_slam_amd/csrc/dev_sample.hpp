@@ -1,8 +1,10 @@
 // Device helpers of the ray generation / depth-guided sampling kernels (sample.hip) -- shared with the fused tracker iteration
 // (track_fused.inc).  Every product or sum that decides a value bit for bit is spelled __fmul_rn / __fadd_rn / __dmul_rn, so
-// the result does not depend on the translation unit's -ffp-contract setting.
+// the result does not depend on the translation unit's -ffp-contract setting -- through dev_rn.hpp's spellings DNS_FMUL ..., which
+// says why the intrinsics alone do not achieve that.
 #pragma once
 #include "common.hpp"
+#include "dev_rn.hpp"
 
 namespace dns {
 
@@ -28,27 +30,27 @@ __device__ __forceinline__ double min_nan(double a, double b) { return (a != a |
 
 __device__ __forceinline__ void quat_to_R(const float* __restrict__ q, float R[9]) {
   const float qr = q[0], qi = q[1], qj = q[2], qk = q[3];
-  const float nrm = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(qr, qr), __fmul_rn(qi, qi)), __fmul_rn(qj, qj)), __fmul_rn(qk, qk));
+  const float nrm = DNS_FADD(DNS_FADD(DNS_FADD(DNS_FMUL(qr, qr), DNS_FMUL(qi, qi)), DNS_FMUL(qj, qj)), DNS_FMUL(qk, qk));
   const float two_s = 2.0f / nrm;
-  const float jj = __fmul_rn(qj, qj), kk = __fmul_rn(qk, qk), ii = __fmul_rn(qi, qi);
-  const float ij = __fmul_rn(qi, qj), kr = __fmul_rn(qk, qr), ik = __fmul_rn(qi, qk), jr = __fmul_rn(qj, qr);
-  const float jk = __fmul_rn(qj, qk), ir = __fmul_rn(qi, qr);
-  R[0] = __fsub_rn(1.0f, __fmul_rn(two_s, __fadd_rn(jj, kk)));
-  R[1] = __fmul_rn(two_s, __fsub_rn(ij, kr));
-  R[2] = __fmul_rn(two_s, __fadd_rn(ik, jr));
-  R[3] = __fmul_rn(two_s, __fadd_rn(ij, kr));
-  R[4] = __fsub_rn(1.0f, __fmul_rn(two_s, __fadd_rn(ii, kk)));
-  R[5] = __fmul_rn(two_s, __fsub_rn(jk, ir));
-  R[6] = __fmul_rn(two_s, __fsub_rn(ik, jr));
-  R[7] = __fmul_rn(two_s, __fadd_rn(jk, ir));
-  R[8] = __fsub_rn(1.0f, __fmul_rn(two_s, __fadd_rn(ii, jj)));
+  const float jj = DNS_FMUL(qj, qj), kk = DNS_FMUL(qk, qk), ii = DNS_FMUL(qi, qi);
+  const float ij = DNS_FMUL(qi, qj), kr = DNS_FMUL(qk, qr), ik = DNS_FMUL(qi, qk), jr = DNS_FMUL(qj, qr);
+  const float jk = DNS_FMUL(qj, qk), ir = DNS_FMUL(qi, qr);
+  R[0] = DNS_FSUB(1.0f, DNS_FMUL(two_s, DNS_FADD(jj, kk)));
+  R[1] = DNS_FMUL(two_s, DNS_FSUB(ij, kr));
+  R[2] = DNS_FMUL(two_s, DNS_FADD(ik, jr));
+  R[3] = DNS_FMUL(two_s, DNS_FADD(ij, kr));
+  R[4] = DNS_FSUB(1.0f, DNS_FMUL(two_s, DNS_FADD(ii, kk)));
+  R[5] = DNS_FMUL(two_s, DNS_FSUB(jk, ir));
+  R[6] = DNS_FMUL(two_s, DNS_FSUB(ik, jr));
+  R[7] = DNS_FMUL(two_s, DNS_FADD(jk, ir));
+  R[8] = DNS_FSUB(1.0f, DNS_FMUL(two_s, DNS_FADD(ii, jj)));
 }
 
 __device__ __forceinline__ void pixel_dir(int64_t q, int H0, int W0, int wwin, Cam cam, int& row, int& col, float dir[3]) {
   row = H0 + (int)(q / wwin);
   col = W0 + (int)(q % wwin);
-  dir[0] = __fdiv_rn(__fsub_rn((float)col, cam.cx), cam.fx);
-  dir[1] = -__fdiv_rn(__fsub_rn((float)row, cam.cy), cam.fy);
+  dir[0] = DNS_FDIV(DNS_FSUB((float)col, cam.cx), cam.fx);
+  dir[1] = -DNS_FDIV(DNS_FSUB((float)row, cam.cy), cam.fy);
   dir[2] = -1.0f;
 }
 
@@ -59,7 +61,7 @@ __device__ __forceinline__ void sample_and_sort(float gd, double far, float dmax
                                                 const float* __restrict__ t_surf, const float* __restrict__ t_zero,
                                                 int nu, int ns, uint32_t lane, uint32_t (&key)[E]) {
   const int S = nu + ns;
-  const double hi = (double)__fmul_rn(dmax, 1.2f);
+  const double hi = (double)DNS_FMUL(dmax, 1.2f);
   double farc = far;                      // torch.clamp(far, 0, hi): NaN propagates
   if (farc == farc) {
     farc = farc < 0.0 ? 0.0 : farc;
@@ -71,17 +73,17 @@ __device__ __forceinline__ void sample_and_sort(float gd, double far, float dmax
     float zv;
     if (s < nu) {
       const float tv = t_uniform[s];
-      const float near = __fmul_rn(gd, 0.001f);
-      const float a = __fmul_rn(near, __fsub_rn(1.0f, tv));
-      zv = (float)__dadd_rn((double)a, __dmul_rn(farc, (double)tv));
+      const float near = DNS_FMUL(gd, 0.001f);
+      const float a = DNS_FMUL(near, DNS_FSUB(1.0f, tv));
+      zv = (float)DNS_DADD((double)a, DNS_DMUL(farc, (double)tv));
     } else if (s < S) {
       const int k = s - nu;
       if (gd > 0.f) {
         const float t = t_surf[k];
-        zv = __fadd_rn(__fmul_rn(__fmul_rn(0.95f, gd), __fsub_rn(1.0f, t)), __fmul_rn(__fmul_rn(1.05f, gd), t));
+        zv = DNS_FADD(DNS_FMUL(DNS_FMUL(0.95f, gd), DNS_FSUB(1.0f, t)), DNS_FMUL(DNS_FMUL(1.05f, gd), t));
       } else {
         const float t = t_zero[k];
-        zv = __fadd_rn(__fmul_rn(0.001f, __fsub_rn(1.0f, t)), __fmul_rn(dmax, t));
+        zv = DNS_FADD(DNS_FMUL(0.001f, DNS_FSUB(1.0f, t)), DNS_FMUL(dmax, t));
       }
     } else {
       zv = 0.f;

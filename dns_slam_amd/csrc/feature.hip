@@ -110,13 +110,7 @@ __global__ void refer_poses_kernel(const float* __restrict__ quat, const float* 
   double A[9], t[3];
   const int k = src[rr];
   if (k >= 0) {
-    const float qw = quat[4 * k], qx = quat[4 * k + 1], qy = quat[4 * k + 2], qz = quat[4 * k + 3];
-    const float two_s = 2.0f / (qw * qw + qx * qx + qy * qy + qz * qz);
-    const float Rm[9] = {1.0f - two_s * (qy * qy + qz * qz), two_s * (qx * qy - qz * qw), two_s * (qx * qz + qy * qw),
-                         two_s * (qx * qy + qz * qw), 1.0f - two_s * (qx * qx + qz * qz), two_s * (qy * qz - qx * qw),
-                         two_s * (qx * qz - qy * qw), two_s * (qy * qz + qx * qw), 1.0f - two_s * (qx * qx + qy * qy)};
-    for (int i = 0; i < 9; ++i) A[i] = (double)Rm[i];
-    for (int i = 0; i < 3; ++i) t[i] = (double)trans[3 * k + i];
+    pose_from_quat(quat + 4 * k, trans + 3 * k, A, t);             // (dev_feature.hpp: shared with the fused tracker's following views)
   } else {
     const float* c = fixed_c2w + 16 * rr;
     for (int i = 0; i < 3; ++i) {
@@ -124,19 +118,7 @@ __global__ void refer_poses_kernel(const float* __restrict__ quat, const float* 
       t[i] = (double)c[4 * i + 3];
     }
   }
-  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
-  const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
-  const double id = 1.0 / det;
-  const double I[9] = {c00 * id, (A[2] * A[7] - A[1] * A[8]) * id, (A[1] * A[5] - A[2] * A[4]) * id,
-                       c01 * id, (A[0] * A[8] - A[2] * A[6]) * id, (A[2] * A[3] - A[0] * A[5]) * id,
-                       c02 * id, (A[1] * A[6] - A[0] * A[7]) * id, (A[0] * A[4] - A[1] * A[3]) * id};
-  float* o = w2c + 16 * rr;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) o[4 * i + j] = (float)I[3 * i + j];
-    o[4 * i + 3] = (float)(-(I[3 * i] * t[0] + I[3 * i + 1] * t[1] + I[3 * i + 2] * t[2]));
-  }
-  o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f;
-  for (int i = 0; i < 3; ++i) origin[3 * rr + i] = (float)t[i];
+  pose_inverse(A, t, w2c + 16 * rr, origin + 3 * rr);
 }
 
 // Backward of (mean over the R references, truncation mask): d_lat[f, r, pl, c] = d_code[p, c] * trunc(p) / R for every r

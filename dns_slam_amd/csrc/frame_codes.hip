@@ -50,36 +50,7 @@ struct Args {
   uint32_t* err;
 };
 
-// one (point, view) pair's code -> dst[0 .. C) (16-byte aligned), lane `sub` of the pair's 16: what feature_gather4_kernel does
-// with dev_feature.hpp's functions.  Not valid, or not kept: zeros, and no tap is read.
-__device__ __forceinline__ void pair_code(const Args& a, uint32_t r, size_t p, bool kept, uint32_t sub, float* __restrict__ dst) {
-  const float x = a.pts[p * 3], y = a.pts[p * 3 + 1], z = a.pts[p * 3 + 2];
-  const int H = a.H, W = a.W, h = a.h, w = a.w;
-  const FeaturePixel q = feature_project(a.w2c + 16 * r, a.K, x, y, z, H, W, kept);
-  const uint32_t C = a.C, C4 = C / 4u;
-  float4* out = reinterpret_cast<float4*>(dst);
-  if (!q.ok) {
-    for (uint32_t c = sub; c < C4; c += 16) out[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    return;
-  }
-  const FeatureTaps t = feature_taps(q.u, q.v, h, w, H, W);
-  const float* f = a.feat + (size_t)r * h * w * C;
-  const float4* f00 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x0) * C);
-  const float4* f01 = reinterpret_cast<const float4*>(f + ((size_t)t.y0 * w + t.x1) * C);
-  const float4* f10 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x0) * C);
-  const float4* f11 = reinterpret_cast<const float4*>(f + ((size_t)t.y1 * w + t.x1) * C);
-  feature_row<16>(f00, f01, f10, f11, t.lx, t.ly, C4, sub, out);
-}
-
-// rel = p - o_r (fp32, utils/common.py:675), normalised with the bound in fp64 (dev_encode.hpp load_point's expression)
-__device__ __forceinline__ void pair_rel(const Args& a, uint32_t r, size_t p, float (&x)[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float rel = a.pts[p * 3 + k] - a.origin[r * 3 + k];
-    x[k] = (float)(((double)rel - a.b0[k]) / (a.b1[k] - a.b0[k]));
-  }
-}
+// (a pair's code and its normalised relative point: pair_code / pair_rel of dev_feature.hpp, shared with track_fused.inc)
 
 namespace {
 
@@ -114,7 +85,8 @@ __global__ __launch_bounds__(256) void frame_codes_kernel(Args a) {
           const uint32_t r = i / npts, pl = i - r * npts;
           const size_t p = (size_t)p0 + pl;
           const bool kept = a.keep == nullptr || a.keep[p] != 0;
-          pair_code(a, r, p, kept, sub, rows + (size_t)i * ld + pe);
+          pair_code(a.w2c + 16 * r, a.K, a.feat + (size_t)r * a.h * a.w * a.C, a.C, a.h, a.w, a.H, a.W, a.pts[p * 3], a.pts[p * 3 + 1],
+                    a.pts[p * 3 + 2], kept, sub, rows + (size_t)i * ld + pe);
         }
       }
     }
@@ -123,8 +95,11 @@ __global__ __launch_bounds__(256) void frame_codes_kernel(Args a) {
       const uint32_t i = i0 + tid;
       if (i < nrows) {
         const uint32_t r = i / npts, pl = i - r * npts;
+        const size_t p = (size_t)p0 + pl;
+        const float pt[3] = {a.pts[p * 3], a.pts[p * 3 + 1], a.pts[p * 3 + 2]};
+        const float og[3] = {a.origin[r * 3], a.origin[r * 3 + 1], a.origin[r * 3 + 2]};
         float x[3];
-        pair_rel(a, r, (size_t)p0 + pl, x);
+        pair_rel(pt, og, a.b0, a.b1, x);
         lds_fp rowp = tile + tid * (pe + 1u);
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) oneblob_axis_fwd(x[ax], a.n_bins, rowp + ax * a.n_bins);

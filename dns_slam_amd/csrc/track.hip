@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include "mlp_split.hpp"
 #include "track_fused.hpp"
+#include "track_stem_plan.hpp"
 
 namespace dns {
 
@@ -33,6 +34,18 @@ static TrackWs track_ws(uint32_t N, uint32_t S, uint32_t ld, uint32_t L, uint32_
 
 static uint32_t rays_per_wg(uint32_t S) { return S <= 32u ? 4u : 2u; }
 
+// LDS of the network phases: the three networks' or, in the stem form, the four networks'
+static uint32_t track_mlp_lds(const DnsTrackFused* a, uint32_t mtl) {
+  const uint32_t io = 3u * a->n_bins + a->n_feat;
+  const bool big = a->n_neurons == 64;
+  if (a->maps) return big ? tf::track_fused_stem_mlp_lds_64_2(io, mtl, a->merge_in, a->merge_out) : tf::track_fused_stem_mlp_lds_32_1(io, mtl, a->merge_in, a->merge_out);
+  return big ? tf::track_fused_mlp_lds_64_2(io, mtl) : tf::track_fused_mlp_lds_32_1(io, mtl);
+}
+// the stem form's slices behind the kernel's other rows (track_stem_plan.hpp)
+static tfs::StemPlan track_stem_plan(const DnsTrackFused* a, uint32_t S, uint32_t mtl, uint64_t base) {
+  return tfs::stem_plan(a->n_rays, S, rays_per_wg(S), a->n_views, 3u * a->merge_bins, a->map_c, a->merge_out, track_mlp_lds(a, mtl), tf::TF_KEEP_BYTES, base);
+}
+
 }  // namespace dns
 
 using namespace dns;
@@ -56,14 +69,39 @@ static int track_shape(const char* who, const DnsTrackFused* a, uint32_t& ld, ui
   DNS_REQUIRE((a->n_neurons == 64 && a->n_hidden_layers == 2) || (a->n_neurons == 32 && a->n_hidden_layers == 1),
               "%s: networks of %u x %u (the fused iteration is built for 64 x 2 and 32 x 1)", who, a->n_neurons, a->n_hidden_layers);
   mtl = a->n_class <= 32u ? 1u : 2u;
+  if (a->maps) {                               // the stem form
+    DNS_REQUIRE(!a->code, "%s: code and maps are both set (a finished code or the stem maps, not both)", who);
+    DNS_REQUIRE(a->w2c && a->origin && a->w_merge && a->merge_bound, "%s: the stem form needs w2c, origin, w_merge and merge_bound", who);
+    DNS_REQUIRE(a->map_c >= 4u && (a->map_c % 4u) == 0, "%s: %u stem channels (a multiple of 4)", who, a->map_c);
+    DNS_REQUIRE(a->merge_bins >= 1u && a->merge_bins <= 64u && ((3u * a->merge_bins) % 4u) == 0 && a->merge_in == 3u * a->merge_bins + a->map_c,
+                "%s: Merge's input width %u is not 3 x %u OneBlob bins + %u stem channels", who, a->merge_in, a->merge_bins, a->map_c);
+    DNS_REQUIRE(a->merge_in > 64u && a->merge_in <= 128u && (a->merge_in % 8u) == 0, "%s: Merge's input width %u outside (64, 128]", who, a->merge_in);
+    DNS_REQUIRE(a->merge_out == a->hidden && a->hidden == 32u && a->n_feat >= 2u * a->hidden,
+                "%s: Merge's output width %u must be the latent width %u (32 in the stem form), n_feat %u at least twice that", who, a->merge_out,
+                a->hidden, a->n_feat);
+    DNS_REQUIRE(a->n_views >= 1u && a->n_views <= tfs::MAX_VIEWS && (a->follow_mask >> a->n_views) == 0,
+                "%s: %u reference views (1..%u), follow mask 0x%x", who, a->n_views, tfs::MAX_VIEWS, a->follow_mask);
+    DNS_REQUIRE(a->map_h >= 1 && a->map_w >= 1 && (uint64_t)a->n_views * a->map_h * a->map_w * a->map_c < (1ull << 40), "%s: stem maps of %d x %d", who,
+                a->map_h, a->map_w);
+    DNS_REQUIRE((((uintptr_t)a->maps | (uintptr_t)a->w_merge) & 15u) == 0, "%s: maps and w_merge must be 16-byte aligned", who);
+  }
   return DNS_OK;
 }
+
+extern "C" uint64_t dns_track_fused_args_bytes(void) { return sizeof(DnsTrackFused); }
 
 extern "C" uint64_t dns_track_fused_ws_floats(const DnsTrackFused* a) {
   uint32_t ld, mtl;
   if (track_shape("dns_track_fused_ws_floats", a, ld, mtl) != DNS_OK) return 0;
   const uint32_t S = a->n_uniform + a->n_surface;
-  return track_ws(a->n_rays, S, ld, a->meta->n_levels, a->hidden, a->n_feat, a->n_class, rays_per_wg(S)).total;
+  const uint64_t base = track_ws(a->n_rays, S, ld, a->meta->n_levels, a->hidden, a->n_feat, a->n_class, rays_per_wg(S)).total;
+  if (!a->maps) return base;
+  const tfs::StemPlan sp = track_stem_plan(a, S, mtl, base);
+  if (!sp.ok) {
+    set_error("dns_track_fused_ws_floats: the stem form's rows / LDS do not fit (%u views, Merge %u -> %u)", a->n_views, a->merge_in, a->merge_out);
+    return 0;
+  }
+  return sp.total_floats;
 }
 
 extern "C" int dns_track_fused_begin(const int64_t* pix_all, uint32_t n_rays, uint32_t n_iters, const float* depth, int W, int H0, int W0,
@@ -98,9 +136,15 @@ extern "C" int dns_track_fused_iter(const DnsTrackFused* a, void* stream) {
   const uint32_t rpw = rays_per_wg(S), n_wg = (N + rpw - 1u) / rpw;
   const TrackWs w = track_ws(N, S, ld, a->meta->n_levels, a->hidden, a->n_feat, a->n_class, rpw);
   const bool big = a->n_neurons == 64;
-  const uint32_t mlp_lds = big ? tf::track_fused_mlp_lds_64_2(pe + a->n_feat, mtl) : tf::track_fused_mlp_lds_32_1(pe + a->n_feat, mtl);
-  DNS_REQUIRE(mlp_lds != 0 && (size_t)mlp_lds + tf::TF_KEEP_BYTES <= (size_t)MAX_DYN_LDS, "dns_track_fused_iter: %u B of LDS for the network phases",
-              mlp_lds);
+  const uint32_t mlp_lds = track_mlp_lds(a, mtl);
+  DNS_REQUIRE(mlp_lds != 0 && (size_t)mlp_lds + tf::TF_KEEP_BYTES + (a->maps ? tfs::VIEWS_BYTES : 0u) <= (size_t)MAX_DYN_LDS,
+              "dns_track_fused_iter: %u B of LDS for the network phases", mlp_lds);
+  tfs::StemPlan sp = {};
+  if (a->maps) {
+    sp = track_stem_plan(a, S, mtl, w.total);
+    DNS_REQUIRE(sp.ok && sp.lds_bytes <= (uint32_t)MAX_DYN_LDS && sp.n_wg == n_wg, "dns_track_fused_iter: the stem form's rows / LDS do not fit (%u views, Merge %u -> %u)",
+                a->n_views, a->merge_in, a->merge_out);
+  }
   tf::TrackArgs t = {};
   t.color = a->color; t.depth = a->depth; t.label = a->label;
   t.H = a->H; t.W = a->W; t.H0 = a->H0; t.W0 = a->W0; t.wwin = a->W1 - a->W0;
@@ -144,5 +188,23 @@ extern "C" int dns_track_fused_iter(const DnsTrackFused* a, void* stream) {
   p.lr_q = a->lr_quat; p.lr_t = a->lr_trans; p.beta1 = a->beta1; p.beta2 = a->beta2; p.eps = a->eps;
   p.iter = a->iter;
   p.best_loss = a->best_loss; p.best_cam = a->best_cam; p.out = a->out; p.g_quat = a->g_quat; p.g_trans = a->g_trans;
+  if (a->maps) {
+    tf::StemArgs s = {};
+    s.maps = a->maps; s.w2c = a->w2c; s.origin = a->origin; s.follow = a->follow_mask;
+    const float K9[9] = {(float)a->cam[0], 0.f, (float)a->cam[2], 0.f, (float)a->cam[1], (float)a->cam[3], 0.f, 0.f, 1.f};
+    for (int k = 0; k < 9; ++k) s.K[k] = K9[k];
+    s.w_merge = reinterpret_cast<const unsigned char*>(a->w_merge);
+    s.fwdb_merge = mlp_prepared_fwd_bytes(a->merge_in, a->merge_out, a->n_neurons, a->n_hidden_layers);
+    for (int k = 0; k < 3; ++k) {
+      s.b0[k] = a->merge_bound[2 * k];
+      s.b1[k] = a->merge_bound[2 * k + 1];
+    }
+    s.R = a->n_views; s.Cs = a->map_c; s.n_bins = a->merge_bins; s.h = a->map_h; s.w = a->map_w;
+    s.ws = ws + sp.base;
+    s.slice_floats = sp.slice_floats; s.rows = sp.rows; s.lat = sp.lat; s.dy = sp.dy; s.dpe = sp.dpe; s.xm = sp.xm; s.drel = sp.drel;
+    s.views_off = sp.views_off;
+    t.keep_off = sp.keep_off;
+    return big ? tf::launch_track_fused_stem_64_2(t, s, p, n_wg, mtl, st) : tf::launch_track_fused_stem_32_1(t, s, p, n_wg, mtl, st);
+  }
   return big ? tf::launch_track_fused_64_2(t, p, n_wg, mtl, st) : tf::launch_track_fused_32_1(t, p, n_wg, mtl, st);
 }

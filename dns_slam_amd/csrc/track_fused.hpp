@@ -60,7 +60,25 @@ struct TrackArgs {
   uint32_t* err;
 };
 
-constexpr uint32_t TF_RAY_FLOATS = 224;      // per ray: z[64] w[64] dsem[64] | o d dir gtc (12) gd valid label pad | loss[4] pose[12]
+// The stem form (DNS_TF_STEM, track_fused_stem_*.hip): the 2-D branch of a stem-trained map inside the iteration -- the second
+// kernel argument.  Row (r, pl) of a workgroup = r * npts + pl in its slice (track_stem_plan.hpp).
+struct StemArgs {
+  const float* maps;                         // [R, h, w, Cs] channels-last stem maps
+  const float* w2c;                          // [R, 16]
+  const float* origin;                       // [R, 3]
+  uint32_t follow;                           // bit r: view r takes its pose from (quat, trans) at kernel entry
+  float K[9];
+  const unsigned char* w_merge;              // prepared operand images of Merge (dns_mlp_prepare)
+  uint32_t fwdb_merge;
+  double b0[3], b1[3];                       // Merge's bound
+  uint32_t R, Cs, n_bins;                    // views, channels, Merge's OneBlob bins
+  int h, w;
+  float* ws;                                 // first workgroup's slice; the offsets below are inside a slice
+  uint32_t slice_floats, rows, lat, dy, dpe, xm, drel;
+  uint32_t views_off;                        // byte offset of the views' poses in LDS (behind the persistent region)
+};
+
+constexpr uint32_t TF_RAY_FLOATS = 224;     // per ray: z[64] w[64] dsem[64] | o d dir gtc (12) gd valid label pad | loss[4] pose[12]
 constexpr uint32_t TF_DX_FLOATS = 4 * 64 * 3;
 constexpr uint32_t TF_KEEP_BYTES = (4 * TF_RAY_FLOATS + TF_DX_FLOATS) * 4;
 
@@ -88,6 +106,11 @@ int launch_track_fused_32_1(const TrackArgs& a, const PoseArgs& p, uint32_t n_wg
 // LDS bytes of the MLP phases of one workgroup (the persistent region follows), 0 = unsupported shape
 uint32_t track_fused_mlp_lds_64_2(uint32_t n_in_out, uint32_t mtl);
 uint32_t track_fused_mlp_lds_32_1(uint32_t n_in_out, uint32_t mtl);
+// the stem form: the same with the 2-D branch inside (track_fused_stem_*.hip); n_in_merge = Merge's input width
+int launch_track_fused_stem_64_2(const TrackArgs& a, const StemArgs& s, const PoseArgs& p, uint32_t n_wg, uint32_t mtl, hipStream_t st);
+int launch_track_fused_stem_32_1(const TrackArgs& a, const StemArgs& s, const PoseArgs& p, uint32_t n_wg, uint32_t mtl, hipStream_t st);
+uint32_t track_fused_stem_mlp_lds_64_2(uint32_t n_in_out, uint32_t mtl, uint32_t n_in_merge, uint32_t hid);
+uint32_t track_fused_stem_mlp_lds_32_1(uint32_t n_in_out, uint32_t mtl, uint32_t n_in_merge, uint32_t hid);
 int launch_track_begin(const int64_t* pix, uint32_t N, uint32_t n_iters, const float* depth, int W, int H0, int W0, int wwin,
                        float* t_surf, uint32_t ns, uint32_t half_idx, uint32_t* dmax, hipStream_t st);
 

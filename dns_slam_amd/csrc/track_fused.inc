@@ -23,12 +23,22 @@
 // The pose kernel (one workgroup) adds the workgroups' partial sums in a fixed order, forms the loss, keeps the best pose
 // (tracking.py:326-335), runs the quaternion chain rule (utils/common.py:406-429) and Adam (torch.optim.Adam semantics, adam.hip).
 #include <type_traits>
+#ifdef DNS_TF_STEM
+#define DNS_RN_NO_CONTRACT                   // dev_rn.hpp: sampling and grid cells round as sample.hip's / encode.hip's do
+#define DNS_TF_FP _Pragma("clang fp contract(off)")
+#else
+#define DNS_TF_FP
+#endif
 #define DNS_BWD_BODY_ONLY
 #include "mlp_split_bwd.inc"
 #include "dev_sample.hpp"
 #include "dev_encode.hpp"
 #include "dev_composite.hpp"
 #include "track_fused.hpp"
+#ifdef DNS_TF_STEM
+#include "dev_feature.hpp"
+#include "track_stem_plan.hpp"
+#endif
 
 namespace dns {
 namespace tf {
@@ -56,8 +66,27 @@ __device__ __forceinline__ RayLds ray_lds(lds_fp keep, uint32_t r) {
 //  linkage the two instantiations share one mangled name and the linker keeps one of them for both launchers)
 namespace {
 
+// The STEM form (DNS_TF_STEM, track_fused_stem_*.hip; DESIGN 4.23): the 2-D branch of a stem-trained map -- feature_matching +
+// Decoder.merge on the iteration's points (slams/tracking.py:162-165), which depends on the pose and so cannot be finished ahead
+// of the loop -- runs inside the kernel.  With R reference views the workgroup owns R npts (point, view) rows, row (r, pl) at
+// r npts + pl, in a private slice of the workspace (track_stem_plan.hpp).  Added phases:
+//   3a  per row: projection, bilinear taps, code (pair_code, dev_feature.hpp: frame_codes.hip's phase A) and the OneBlob columns
+//       of rel = p - o_r normalised with Merge's bound (pair_rel), through the LDS staging tile.  A pair outside its view, or of
+//       a sample outside the truncation band (its code is multiplied by 0 below and receives no gradient), is a zero code
+//       and reads no tap.  A FOLLOWING view (slams/tracking.py:316-319) takes its pose from (quat, trans) at kernel entry.
+//   3b  Merge forward on the rows (tiles_per_block = R)
+//   3c  inside phase 3: the code = the views' sum in ascending view order x 1 / R x truncation mask (dns_feature_block_split's order)
+//   6a  behind the colour / logit backward: d_lat(r, p) = d_code(p) trunc(p) / R (dns_merge_dy), Merge backward (input gradient of
+//       the first segment only: DNS_MLP_DX_FIRST's form), OneBlob backward, d rel = d x / (b1 - b0) in fp64
+//   7   d pts += the views' d rel in ascending view order (dns_add_ref_sum), behind the encoder's share
+// No atomics, fixed orders.  NCHM: Merge's input width in 32-column chunks (3 or 4).
+#ifdef DNS_TF_STEM
+template <int MTL, int NCHO, int NCHM>
+__global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a, StemArgs sa) {
+#else
 template <int MTL, int NCHO>
 __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
+#endif
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr uint32_t NCHC = 3, MTC = 2;                       // coarse: 65..96 inputs, 33..64 outputs; colour / logit: NCHO = 3 (65..96) or 4 (97..128)
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -74,9 +103,30 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
   lds_fp tile = (lds_fp)lds;                                      // [points of the workgroup][ld + 1] staging tile of phases 1 and 7
   lds_fp keep = (lds_fp)(lds + a.keep_off);                       // persists across the MLP phases (they use [0, keep_off))
   lds_fp dxp = keep + 4 * TF_RAY_FLOATS;
+#ifdef DNS_TF_STEM
+  // the views' poses (first three rows of w2c | origin) in LDS behind the persistent region: a following view's from the pose
+  // this iteration's rays are cast from (refer_poses_kernel's arithmetic, dev_feature.hpp), the others' as stored.  Read from
+  // phase 3a on, behind phase 1's barriers.
+  lds_fp views = (lds_fp)(lds + sa.views_off);
+  if (threadIdx.x < sa.R) {
+    const uint32_t r = threadIdx.x;
+    lds_fp v = views + r * tfs::VIEW_FLOATS;
+    if ((sa.follow >> r) & 1u) {
+      double A[9], t[3];
+      pose_from_quat(a.quat, a.trans, A, t);
+      pose_inverse<true>(A, t, v, v + 12);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) v[k] = sa.w2c[16u * r + k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[12 + k] = sa.origin[3u * r + k];
+    }
+  }
+#endif
 
   // ---- 1: rays, samples, encoding ---------------------------------------------------------------------------------------
   {
+    DNS_TF_FP                                  // (stem form: d, pts and their normalisation round as raygen_sample_kernel / load_point do)
     const uint32_t r = wave / wpr, part = wave - r * wpr, n = n0 + r;
     if (n < n1) {
       int row, col;
@@ -89,7 +139,7 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         o[k] = a.trans[k];
-        d[k] = __fadd_rn(__fadd_rn(__fmul_rn(dir[0], R[3 * k]), __fmul_rn(dir[1], R[3 * k + 1])), __fmul_rn(dir[2], R[3 * k + 2]));
+        d[k] = DNS_FADD(DNS_FADD(DNS_FMUL(dir[0], R[3 * k]), DNS_FMUL(dir[1], R[3 * k + 1])), DNS_FMUL(dir[2], R[3 * k + 2]));
       }
       const float gd = a.depth[pixi];
       double far = 0.0;
@@ -124,7 +174,7 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
         float x[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          const float pt = __fadd_rn(o[k], __fmul_rn(d[k], zv));
+          const float pt = DNS_FADD(o[k], DNS_FMUL(d[k], zv));
           x[k] = (float)(((double)pt - a.b6.b0[k]) / (a.b6.b1[k] - a.b6.b0[k]));
         }
         // the point's row goes to an LDS tile (row stride ld + 1: conflict-free for lane = point; the MLP phases' LDS is free
@@ -191,6 +241,91 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
   __syncthreads();
 
   if (a.n_phases == 2u) return;
+#ifdef DNS_TF_STEM
+  // ---- 3a: the (point, view) rows of the 2-D branch: code | OneBlob of the normalised relative point -------------------------
+  float* __restrict__ slice = sa.ws + (size_t)wg * sa.slice_floats;
+  float* __restrict__ mrows = slice + sa.rows;
+  float* __restrict__ mlat = slice + sa.lat;
+  float* __restrict__ mdy = slice + sa.dy;
+  float* __restrict__ mdpe = slice + sa.dpe;
+  float* __restrict__ mxm = slice + sa.xm;
+  float* __restrict__ mdrel = slice + sa.drel;
+  const uint32_t pe_m = 3u * sa.n_bins, ldm = pe_m + sa.Cs, R = sa.R, nrows = R * npts;
+  // the point of row i's sample (phase 1's expression) and whether its code is kept (truncation mask != 0)
+  auto row_point = [&](uint32_t pl, float (&pt)[3]) __attribute__((always_inline)) -> bool {
+    DNS_TF_FP
+    const uint32_t rr = pl / S;
+    const RayLds rl = ray_lds(keep, rr);
+    const float zv = rl.z[pl - rr * S], gd = rl.m[12];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) pt[k] = DNS_FADD(rl.m[k], DNS_FMUL(rl.m[3 + k], zv));
+    return !(zv < gd * 0.95f) && !(zv > gd * 1.05f) && gd > 0.f;
+  };
+  {
+    Mat3 Km;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Km.k[k] = sa.K[k];
+    const uint32_t sub = threadIdx.x & 15u;
+    const size_t map_floats = (size_t)sa.h * sa.w * sa.Cs;
+    // codes: 16 lanes per pair, 16 pairs per pass of the workgroup (frame_codes.hip phase A)
+#pragma unroll 1
+    for (uint32_t i0 = 0; i0 < nrows; i0 += 16u) {
+      const uint32_t i = i0 + (threadIdx.x >> 4);
+      if (i < nrows) {
+        const uint32_t r = i / npts, pl = i - r * npts;
+        float pt[3], m[12];
+        const bool kept = row_point(pl, pt);
+        const lds_fp v = views + r * tfs::VIEW_FLOATS;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) m[k] = v[k];
+        pair_code(m, Km, sa.maps + (size_t)r * map_floats, sa.Cs, sa.h, sa.w, a.H, a.W, pt[0], pt[1], pt[2], kept, sub,
+                  mrows + (size_t)i * ldm + pe_m);
+      }
+    }
+    // OneBlob: one row per thread into the LDS tile, then out as contiguous float4 runs
+    for (uint32_t i0 = 0; i0 < nrows; i0 += tfs::PE_ROWS) {
+      const uint32_t i = i0 + threadIdx.x;
+      if (i < nrows) {
+        const uint32_t r = i / npts, pl = i - r * npts;
+        float pt[3], x[3];
+        row_point(pl, pt);
+        const lds_fp v = views + r * tfs::VIEW_FLOATS;
+        const float og[3] = {v[12], v[13], v[14]};
+        pair_rel(pt, og, sa.b0, sa.b1, x);
+        mxm[(size_t)i * 3 + 0] = x[0];
+        mxm[(size_t)i * 3 + 1] = x[1];
+        mxm[(size_t)i * 3 + 2] = x[2];
+        lds_fp rowp = tile + threadIdx.x * (pe_m + 1u);
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) oneblob_axis_fwd(x[ax], sa.n_bins, rowp + ax * sa.n_bins);
+      }
+      __syncthreads();
+      const uint32_t nq = pe_m / 4u, cnt = min(tfs::PE_ROWS, nrows - i0);
+      for (uint32_t j = threadIdx.x; j < cnt * nq; j += blockDim.x) {
+        const uint32_t rr = j / nq, c = j - rr * nq;
+        const lds_fp s = tile + rr * (pe_m + 1u) + 4u * c;
+        *reinterpret_cast<float4*>(mrows + (size_t)(i0 + rr) * ldm + 4u * c) = make_float4(s[0], s[1], s[2], s[3]);
+      }
+      __syncthreads();
+    }
+  }
+  if (a.n_phases == 31u) return;
+  // ---- 3b: Merge forward on the rows ------------------------------------------------------------------------------------------
+  {
+    sp::FwdArgs fm = {};
+    fm.x = mrows; fm.ldx = ldm;
+    fm.seg = {nullptr, 0u, ldm};
+    fm.n_in = ldm; fm.n_in_w = ldm; fm.n_out = hid;
+    fm.y = mlat; fm.ldy = hid;
+    fm.n_slots = nrows; fm.tiles_per_block = R;
+    fm.err = a.err;
+    fm.prep = sa.w_merge;
+    __builtin_assume(fm.prep != nullptr);
+    sp::mlp_fwd_body<NN, NL, 3>(fm, 0u, lds);
+  }
+  __syncthreads();
+  if (a.n_phases == 32u) return;
+#endif
   // ---- 3: feature block [latent | code x truncation mask], raw[:, 3] = occupancy ---------------------------------------------
   // Without a 2-D code (nf == hid: the colour / logit images are those of the LIVE network, DNS_MLP_LIVE_IN(pe + hid)) there is
   // no block to build: the two networks read the latent straight out of the coarse network's output rows (second input
@@ -207,6 +342,24 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
       if (q < qh) {
         v = make_float4(f[1 + 4 * q], f[2 + 4 * q], f[3 + 4 * q], f[4 + 4 * q]);
         if (q == 0u) a.raw[(size_t)p * 4 + 3] = f[0];
+#ifdef DNS_TF_STEM
+      } else if (4u * (q - qh) < hid) {
+        // 3c: the code = Merge's latents summed over the views in ascending view order, x 1 / R, x truncation mask
+        const uint32_t rr = pl / S;
+        const RayLds rl = ray_lds(keep, rr);
+        const float d = rl.m[12], zz = rl.z[pl - rr * S];
+        const float front = zz < d * 0.95f ? 1.f : 0.f, back = zz > d * 1.05f ? 1.f : 0.f, pos = d > 0.f ? 1.f : 0.f;
+        const float t = (1.f - front) * (1.f - back) * pos;
+        const float inv_ref = R > 1u ? 1.0f / (float)R : 1.0f;
+        const float* c0 = mlat + (size_t)pl * hid + 4u * (q - qh);
+        float4 cv = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (uint32_t r = 0; r < R; ++r) {
+          const float4 u = *reinterpret_cast<const float4*>(c0 + (size_t)r * npts * hid);
+          cv.x += u.x; cv.y += u.y; cv.z += u.z; cv.w += u.w;
+        }
+        if (R > 1u) { cv.x *= inv_ref; cv.y *= inv_ref; cv.z *= inv_ref; cv.w *= inv_ref; }
+        v = make_float4(cv.x * t, cv.y * t, cv.z * t, cv.w * t);
+#endif
       } else if (a.code && 4u * (q - qh) < a.code_dim) {
         const uint32_t rr = pl / S;
         const RayLds rl = ray_lds(keep, rr);
@@ -381,6 +534,66 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
     ba.prep = a.w_logit + a.fwdb_logit;
     __builtin_assume(ba.prep != nullptr);
     sp::mlp_bwd_body<NCHO, MTL, 3, false, false, false, 4>(ba, 0u, lds);
+#ifdef DNS_TF_STEM
+    // ---- 6a: Merge backward: d code -> the rows' d latent -> d OneBlob -> d(relative point) ------------------------------------
+    __syncthreads();
+    {
+      // d_lat(r, p) = d_code(p) trunc(p) / R for every view (merge_dy_kernel's expression)
+      const uint32_t qh = hid / 4u;
+      const float inv = 1.0f / (float)R;
+      for (uint32_t i = threadIdx.x; i < npts * qh; i += blockDim.x) {
+        const uint32_t pl = i / qh, q = i - pl * qh, rr = pl / S;
+        const RayLds rl = ray_lds(keep, rr);
+        const float d = rl.m[12], zz = rl.z[pl - rr * S];
+        const float front = zz < d * 0.95f ? 1.f : 0.f, back = zz > d * 1.05f ? 1.f : 0.f, pos = d > 0.f ? 1.f : 0.f;
+        const float t = (1.f - front) * (1.f - back) * pos * inv;
+        float4 g = *reinterpret_cast<const float4*>(a.d_featx + (size_t)(p0 + pl) * ldf + 4u + hid + 4u * q);
+        g.x *= t; g.y *= t; g.z *= t; g.w *= t;
+        float* dst = mdy + (size_t)pl * hid + 4u * q;
+        for (uint32_t r = 0; r < R; ++r) *reinterpret_cast<float4*>(dst + (size_t)r * npts * hid) = g;
+      }
+    }
+    __syncthreads();
+    {
+      // input gradient only, first segment only: the two-segment input with no second gradient segment (DNS_MLP_DX_FIRST's form);
+      // the hidden activations are recomputed from the rows of 3a
+      sp::BwdArgs bm = {};
+      bm.x = mrows; bm.ldx = ldm;
+      bm.seg = {mrows + pe_m, ldm, pe_m};
+      bm.dy = mdy; bm.lddy = hid;
+      bm.n_in = ldm; bm.n_in_w = ldm; bm.n_out = hid;
+      bm.dx = mdpe; bm.lddx = pe_m;
+      bm.dseg = {nullptr, 0u, 0u, 0u, 0u};
+      bm.n_slots = nrows; bm.tiles_per_block = R; bm.n_waves = 4; bm.err = a.err;
+      bm.prep = sa.w_merge + sa.fwdb_merge;
+      __builtin_assume(bm.prep != nullptr);
+      sp::mlp_bwd_body<NCHM, 1, 3, false, false, false, 4>(bm, 0u, lds);
+    }
+    __syncthreads();
+    // OneBlob backward: the rows' d OneBlob -> tile (coalesced), one row per thread, d rel = d x / (b1 - b0) in fp64
+    for (uint32_t i0 = 0; i0 < nrows; i0 += tfs::PE_ROWS) {
+      const uint32_t nq = pe_m / 4u, cnt = min(tfs::PE_ROWS, nrows - i0);
+      for (uint32_t j = threadIdx.x; j < cnt * nq; j += blockDim.x) {
+        const uint32_t rr = j / nq, c = j - rr * nq;
+        const float4 v = *reinterpret_cast<const float4*>(mdpe + (size_t)(i0 + rr) * pe_m + 4u * c);
+        const lds_fp t = tile + rr * (pe_m + 1u) + 4u * c;
+        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+      }
+      __syncthreads();
+      const uint32_t i = i0 + threadIdx.x;
+      if (i < nrows) {
+        const lds_fp g = tile + threadIdx.x * (pe_m + 1u);
+        const float x[3] = {mxm[(size_t)i * 3], mxm[(size_t)i * 3 + 1], mxm[(size_t)i * 3 + 2]};
+        float dxm[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) oneblob_axis_bwd(x[ax], sa.n_bins, g + ax * sa.n_bins, dxm[ax]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) mdrel[(size_t)i * 3 + k] = (float)((double)dxm[k] / (sa.b1[k] - sa.b0[k]));
+      }
+      __syncthreads();
+    }
+    if (a.n_phases == 61u) return;
+#endif
     // coarse: dY = [d occupancy | d latent] = d_featx[:, 3 : 4 + hid]; adds to all ld columns of d_buf
     ba.seg = {nullptr, 0u, ld};
     ba.dy = a.d_featx + (size_t)p0 * ldf + 3; ba.lddy = ldf; ba.n_out = hid + 1u;
@@ -395,6 +608,7 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
   if (a.n_phases == 6u) return;
   // ---- 7: encoding backward -> d pts, the rays' sums for the pose -------------------------------------------------------------
   {
+    DNS_TF_FP                                  // (stem form: the grid's dot products round as encode_bwd_kernel's, compiled without contraction)
     {
       // the workgroup's d_buf rows (contiguous) -> tile, coalesced; the lanes then read THEIR row from LDS
       const uint32_t nq = ld / 4u;
@@ -441,6 +655,15 @@ __global__ __launch_bounds__(256, 1) void track_fused_kernel(TrackArgs a) {
           float v = 0.f;
           for (uint32_t q = 0; q < wpr; ++q) v += dxp[((wave + q) * 64u + lane) * 3u + k];
           v = (float)((double)v / (a.b6.b1[k] - a.b6.b0[k]));       // d pts = d x / (b1 - b0) (fp64, encode_bwd_kernel)
+#ifdef DNS_TF_STEM
+          {
+            // + Merge's share: the views' d rel in ascending view order (add_ref_sum_kernel)
+            const float* src = mdrel + (size_t)((n - n0) * S + lane) * 3u + k;
+            float s = 0.f;
+            for (uint32_t q = 0; q < R; ++q) s += src[(size_t)q * npts * 3u];
+            v += s;
+          }
+#endif
           go[k] = v;
           gdv[k] = v * zv;
         }
@@ -588,10 +811,18 @@ static __global__ __launch_bounds__(256) void track_begin_kernel(const int64_t* 
 }
 
 
+#ifdef DNS_TF_STEM
+template <int MTL, int NCHO>
+static bool tf_attr() {
+  return hipFuncSetAttribute((const void*)track_fused_kernel<MTL, NCHO, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess &&
+         hipFuncSetAttribute((const void*)track_fused_kernel<MTL, NCHO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess;
+}
+#else
 template <int MTL, int NCHO>
 static bool tf_attr() {
   return hipFuncSetAttribute((const void*)track_fused_kernel<MTL, NCHO>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS) == hipSuccess;
 }
+#endif
 static int tf_init_attrs() {
   if (!tf_attr<1, 3>() || !tf_attr<2, 3>() || !tf_attr<1, 4>() || !tf_attr<2, 4>()) {
     set_error("dns_init: hipFuncSetAttribute failed for the fused tracker kernel");
@@ -603,6 +834,46 @@ static AttrRegistrar tf_attr_registrar(tf_init_attrs);
 
 #define DNS_TF_CAT(a, b, c) a##b##_##c
 #define DNS_TF_NAME(pfx, nn, nl) DNS_TF_CAT(pfx, nn, nl)
+#ifdef DNS_TF_STEM
+// LDS bytes of the network phases of the stem form: the largest of the four networks' needs (Merge: n_in_merge -> hid, forward and
+// input-gradient backward), 0 = unsupported shape
+uint32_t DNS_TF_NAME(track_fused_stem_mlp_lds_, DNS_BWD_NN, DNS_BWD_NL)(uint32_t n_in_out, uint32_t mtl, uint32_t n_in_merge, uint32_t hid) {
+  using namespace sp;
+  if (n_in_out <= 64u || n_in_out > 128u || mtl < 1u || mtl > 2u || n_in_merge <= 64u || n_in_merge > 128u || hid < 1u || hid > 32u) return 0u;
+  uint32_t m = FwdLds<NN, NL>::total(n_in_out, mtl * 32u, 4);
+  const uint32_t b1 = n_in_out <= 96u ? (mtl == 1u ? BwdLds<3, 1>::total(true, 4) : BwdLds<3, 2>::total(true, 4))
+                                      : (mtl == 1u ? BwdLds<4, 1>::total(true, 4) : BwdLds<4, 2>::total(true, 4));
+  const uint32_t b2 = BwdLds<3, 2>::total(true, 4);
+  const uint32_t f3 = FwdLds<NN, NL>::total(n_in_merge, hid, 4);
+  const uint32_t b3 = n_in_merge <= 96u ? BwdLds<3, 1>::total(true, 4) : BwdLds<4, 1>::total(true, 4);
+  m = m > b1 ? m : b1;
+  m = m > b2 ? m : b2;
+  m = m > f3 ? m : f3;
+  m = m > b3 ? m : b3;
+  return (m + 15u) & ~15u;
+}
+int DNS_TF_NAME(launch_track_fused_stem_, DNS_BWD_NN, DNS_BWD_NL)(const TrackArgs& a, const StemArgs& s, const PoseArgs& p, uint32_t n_wg, uint32_t mtl,
+                                                                  hipStream_t st) {
+  const size_t lds_bytes = (size_t)s.views_off + tfs::VIEWS_BYTES;
+  const bool narrow = 3u * a.n_bins + a.nf <= 96u;             // colour / logit input width: three or four 32-column chunks
+  const bool narrow_m = 3u * s.n_bins + s.Cs <= 96u;           // Merge's
+#define DNS_TF_GO(MTL_, NCHO_)                                                                                              \
+  {                                                                                                                         \
+    if (narrow_m) DNS_LAUNCH((track_fused_kernel<MTL_, NCHO_, 3>), dim3(n_wg), dim3(256), lds_bytes, st, a, s);            \
+    else DNS_LAUNCH((track_fused_kernel<MTL_, NCHO_, 4>), dim3(n_wg), dim3(256), lds_bytes, st, a, s);                     \
+  }
+  if (narrow) {
+    if (mtl == 1u) DNS_TF_GO(1, 3)
+    else DNS_TF_GO(2, 3)
+  } else {
+    if (mtl == 1u) DNS_TF_GO(1, 4)
+    else DNS_TF_GO(2, 4)
+  }
+#undef DNS_TF_GO
+  DNS_LAUNCH(track_pose_kernel, dim3(1), dim3(1024), 0, st, p);
+  return check_launch("dns_track_fused_iter");
+}
+#else
 uint32_t DNS_TF_NAME(track_fused_mlp_lds_, DNS_BWD_NN, DNS_BWD_NL)(uint32_t n_in_out, uint32_t mtl) {
   using namespace sp;
   if (n_in_out <= 64u || n_in_out > 128u || mtl < 1u || mtl > 2u) return 0u;
@@ -627,6 +898,7 @@ int DNS_TF_NAME(launch_track_fused_, DNS_BWD_NN, DNS_BWD_NL)(const TrackArgs& a,
   DNS_LAUNCH(track_pose_kernel, dim3(1), dim3(1024), 0, st, p);
   return check_launch("dns_track_fused_iter");
 }
+#endif  // DNS_TF_STEM
 #ifdef DNS_TF_WITH_BEGIN
 int launch_track_begin(const int64_t* pix, uint32_t N, uint32_t n_iters, const float* depth, int W, int H0, int W0, int wwin,
                        float* t_surf, uint32_t ns, uint32_t half_idx, uint32_t* dmax, hipStream_t st) {

@@ -71,6 +71,17 @@ def _read_scene(o, who, dec, features, refer_frames, maps, refer):
     return nets[:3]
 
 
+def _follow_flags(refer_frames, R):
+    """refer_frames['follow'] as a tuple of R booleans (absent: all False)."""
+    follow = None if refer_frames is None else refer_frames.get("follow")
+    if follow is None:
+        return (False,) * R
+    follow = tuple(bool(v) for v in follow)
+    if len(follow) != R:
+        raise ValueError(f"refer_frames['follow'] holds {len(follow)} flags for {R} reference views")
+    return follow
+
+
 class _Set:
     """What one step's preparation writes: the gradient buffer (zeroed), the fine network's output (zeroed), the draws and what
     derives from them alone (per-frame depth maximum, slot -> row table of the per-class routing)."""
@@ -728,6 +739,10 @@ class TrackStep:
             self.stem2d = Stem2D("TrackStep", dec.merge, 1, R, P, Cs, fh, fw, self.hid, (t.fx, t.fy, t.cx, t.cy), dev,
                                  want_dw=False, want_pose=True)
             self.feat_maps, self.w2c, self.origin = f(R, fh, fw, Cs), f(R, 16), f(R, 3)
+            # refer_frames["follow"]: views that take, in every iteration, the pose being optimised as it stands before that
+            # iteration's update (slams/tracking.py:316-319: cur_w2c from quad, T, detached) instead of the stored est_w2c
+            self.follow = _follow_flags(refer_frames, self.R)
+            self._src0 = torch.zeros(1, device=dev, dtype=torch.int32)
             self._set_views(features, refer_frames)
         self.ray_ws = f(max(int(raw_lib.dns_raygen_bwd_ws_floats(1, N)), 1))
         # The scene is frozen for the whole loop: its networks' operand images are built ONCE (DNS_MLP_PREPARED) and every
@@ -781,6 +796,13 @@ class TrackStep:
         rows.fwd(self.net_c, self.lat, st)                                 # coarse-only render (slams/tracking.py:196-200)
         if self.stem:
             s2 = self.stem2d
+            for r, fl in enumerate(self.follow):
+                # a following view: w2c / origin from the pose as it stands now (dns_refer_poses, src = 0 = "the pose in the
+                # optimiser"), written over the view's own row -- the other rows keep the stored poses bit for bit.  One launch for
+                # the reference's call, follow = (False, True)
+                if fl:
+                    check(lib.dns_refer_poses(ptr(self.Q), ptr(self.T), ptr(self._src0), ptr(self.w2c), 1,
+                                              _V(self.w2c.data_ptr() + 64 * r), _V(self.origin.data_ptr() + 12 * r), st), "dns_refer_poses")
             s2.forward(self.pts, self.w2c, self.origin, self.feat_maps, H, W, self.net_m, st)
             rows.feature_block(self.lat, self.hid, s2.mlat, (self.R, P), self.z, self.gt_depth, N, S, self.raw, st)
         else:
@@ -833,7 +855,7 @@ class TrackStep:
         fs = None if features is None else tuple(features.shape)
         if features is not None and features.dim() == 5:
             nets.append(dec.merge.decoder.params)
-            fs = fs + (tuple(refer_frames["est_w2c"].shape),)
+            fs = fs + (tuple(refer_frames["est_w2c"].shape), _follow_flags(refer_frames, int(features.shape[1])))
         #  also baked into a capture: the networks' precision flag, the device, the level table of the grid (passed by
         # value), the ADDRESS of the shared surface jitter, and -- with stem maps -- Merge's bound and OneBlob bin count
         grid = dec.pe_fn.grid_fn
@@ -899,9 +921,11 @@ class TrackStep:
                 check(ops.lib.dns_mlp_prepare(ptr(p_), shp_[0], shp_[1], shp_[2], shp_[3], 1, 0, ptr(w), live, st), "dns_mlp_prepare")
 
     # ---- the iteration as ONE kernel + a pose kernel (csrc/track_fused.inc, ABI v11) ------------------------------------------
-    def fused_supported(self):
-        """Can ``run_fused`` take this tracker?  (S <= 64, 64 x 2 or 32 x 1 networks, no in-loop stem branch, fp32-grade MLPs.)"""
-        if self.stem or self.fp16 or self.S > 64:
+    def fused_supported(self, stem=False):
+        """Can ``run_fused`` take this tracker?  (S <= 64, 64 x 2 or 32 x 1 networks, fp32-grade MLPs.)  A tracker with the in-loop
+        stem branch is supported by the kernel's stem form (csrc/track_fused_stem_*.hip) but answers False unless asked with
+        ``stem=True``: ``Tracker.track_frame`` routes it there only on ``tracker.fused_stem``."""
+        if (self.stem and not stem) or self.fp16 or self.S > 64:
             return False
         if (self.shp_c[2], self.shp_c[3]) not in ((64, 2), (32, 1)):
             return False
@@ -932,7 +956,18 @@ class TrackStep:
         a.w_coarse, a.w_color, a.w_logit = self.w_coarse.data_ptr(), self.w_color.data_ptr(), self.w_logit.data_ptr()
         a.n_neurons, a.n_hidden_layers = self.shp_c[2], self.shp_c[3]
         a.hidden, a.n_feat, a.n_class = self.hid, self.n_feat, self.n_class
-        if self.features is not None:
+        if self.stem:
+            # the stem form: the maps, the views (copied into place by _set_views, so reset() keeps this block and its captured
+            # graph) and Merge's prepared image; following views as a bit mask
+            s2 = self.stem2d
+            a.code, a.code_dim = 0, 0
+            a.maps, a.w2c, a.origin = self.feat_maps.data_ptr(), self.w2c.data_ptr(), self.origin.data_ptr()
+            a.follow_mask = sum(1 << r for r, fl in enumerate(self.follow) if fl)
+            a.w_merge = self.w_merge.data_ptr()
+            a.merge_in, a.merge_out, a.merge_bins = s2.shape[0], s2.shape[1], s2.n_bins
+            a.merge_bound = C.addressof(s2.b6)
+            a.n_views, a.map_c, a.map_h, a.map_w = self.R, s2.Cs, s2.fh, s2.fw
+        elif self.features is not None:
             a.code, a.code_dim = self.features.data_ptr(), self.features.shape[-1]
         else:
             a.code, a.code_dim = 0, 0

@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .common import feature_matching, get_quad_from_c2w
+from .common import feature_matching, get_quad_from_c2w, get_rotation_from_quad
 
 
 class Tracker:
@@ -37,6 +37,7 @@ class Tracker:
         self.border = 20
         self.static_shapes = False        # True: device-side jitter draws, no host work per iteration (hipGraph-capturable)
         self.use_track_step = False       # True: track_frame runs fused_step.TrackStep (fixed launch sequence, device-side draws)
+        self.fused_stem = False           # True: a stem-trained map's TrackStep runs the fused kernel's stem form (run_fused)
         self.t_uniform = torch.linspace(0.0, 1.0, steps=self.n_samples_ray, device=device) if self.n_samples_ray > 0 else None
         if str(device) != "cpu":
             from ._lib import ensure_init
@@ -179,7 +180,10 @@ class Tracker:
                 self._track_step, self._track_step_key = ts, key
             # round 5: the whole iteration as ONE kernel + a pose kernel (csrc/track_fused.inc) wherever the shape allows it
             # (S <= 64, 64 x 2 / 32 x 1 networks, no in-loop stem branch); use_fused_kernel = False keeps the launch sequence
-            if getattr(self, "use_fused_kernel", True) and ts.fused_supported():
+            # A stem-trained map (in-loop 2-D branch) takes the kernel's stem form only on fused_stem: run_fused draws per frame,
+            # step per iteration, so the two consume the generator differently
+            stem_fused = bool(getattr(self, "fused_stem", False)) and ts.stem
+            if getattr(self, "use_fused_kernel", True) and ts.fused_supported(stem=stem_fused):
                 cam, best = ts.run_fused(n_iters, graph=graph)
             else:
                 cam, best = ts.run(n_iters, graph=graph)
@@ -192,8 +196,38 @@ class Tracker:
                 return self._track_frame_graphed(cur_frames, est_c2w, n_iters, features, graph_warmup, refer_frames)
             return self._track_frame_eager(cur_frames, est_c2w, n_iters, features, fused, refer_frames)
 
+    # slams/tracking.py:316-319: a FOLLOWING view (refer_frames["follow"][r]) takes, in every iteration, w2c = inverse(c2w(quad, T))
+    # of the pose as it stands before that iteration's update, detached
+    def _follow_setup(self, refer_frames):
+        follow = None if refer_frames is None else refer_frames.get("follow")
+        if follow is None or not any(bool(v) for v in follow):
+            return None
+        w2c = refer_frames["est_w2c"].detach().to(self.device).float()
+        if len(follow) != w2c.shape[0]:
+            raise ValueError(f"refer_frames['follow'] holds {len(follow)} flags for {w2c.shape[0]} reference views")
+        mask = torch.tensor([bool(v) for v in follow], device=self.device).reshape(-1, 1, 1)
+        bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]], device=self.device)
+        return {"refer": dict(refer_frames), "w2c": w2c, "mask": mask, "bottom": bottom}
+
+    def _follow_refresh(self, fv, refer_frames, quad, T):
+        """refer_frames for this iteration.  Eager: torch.inverse like the reference; inside a stream capture (torch.inverse checks
+        its result on the host) the affine inverse [R^T | -R^T T] of the rotation get_rotation_from_quad builds, exact to rounding."""
+        if fv is None:
+            return refer_frames
+        with torch.no_grad():
+            Rm = get_rotation_from_quad(quad.detach())
+            Td = T.detach()
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                Rt = Rm.transpose(0, 1)
+                cur = torch.cat([torch.cat((Rt, -(Rt @ Td)[:, None]), -1), fv["bottom"]], 0)
+            else:
+                cur = torch.inverse(torch.cat([torch.cat((Rm, Td[:, None]), -1), fv["bottom"]], 0))
+            fv["refer"]["est_w2c"] = torch.where(fv["mask"], cur[None], fv["w2c"]).contiguous()   # (torch.inverse returns column-major strides)
+        return fv["refer"]
+
     def _track_frame_eager(self, cur_frames, est_c2w, n_iters, features, fused, refer_frames=None):
         optimizer, quad, T = self.set_optimizer(est_c2w, fused=fused)
+        fv = self._follow_setup(refer_frames)
         frames = dict(cur_frames)
         frames["est_quad"], frames["est_T"] = quad, T
         prep = self.prepare_frame(cur_frames)
@@ -201,7 +235,7 @@ class Tracker:
         best_cam = torch.cat((quad, T), 0).detach().clone()
         for _ in range(n_iters):
             optimizer.zero_grad()
-            samples = self.get_target_samples(frames, refer_frames=refer_frames, features=features, prep=prep)
+            samples = self.get_target_samples(frames, refer_frames=self._follow_refresh(fv, refer_frames, quad, T), features=features, prep=prep)
             pred_color, pred_depth, pred_depth_var, pred_logits = self.renderer(samples)
             loss, _terms = ops.tracking_losses(pred_color, pred_depth, pred_depth_var, pred_logits, samples["gt_color"],
                                                samples["gt_depth"], samples["gt_label"], samples["mask"],
@@ -225,10 +259,11 @@ class Tracker:
         prep = self.prepare_frame(cur_frames)
         state = {"best_loss": torch.full((), float("inf"), device=self.device),
                  "best_cam": torch.cat((quad, T), 0).detach().clone()}
+        fv = self._follow_setup(refer_frames)
 
         def one_iter():
             optimizer.zero_grad(set_to_none=True)
-            samples = self.get_target_samples(frames, refer_frames=refer_frames, features=features, prep=prep)
+            samples = self.get_target_samples(frames, refer_frames=self._follow_refresh(fv, refer_frames, quad, T), features=features, prep=prep)
             pc, pd, pv, pl = self.renderer(samples)
             loss, _ = ops.tracking_losses(pc, pd, pv, pl, samples["gt_color"], samples["gt_depth"], samples["gt_label"],
                                           samples["mask"], (self.lambda_p, self.lambda_d, self.lambda_l))

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 24
+#define DNS_ABI_VERSION 25
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -487,7 +487,24 @@ typedef struct DnsTrackFused {
   float* out;
   float* g_quat;
   float* g_trans;
+  /* ---- the stem form (ABI v25): maps != NULL runs the 2-D branch of a stem-trained map INSIDE the iteration (feature_matching +
+   * Decoder.merge on the iteration's points, slams/tracking.py:162-165; Merge frozen like the scene).  maps NULL: as before.
+   *   maps [n_views, map_h, map_w, map_c] channels-last half-resolution stem maps (16-byte aligned, map_c % 4 == 0);
+   *   w2c [n_views, 16], origin [n_views, 3]: the reference views; bit r of follow_mask: view r takes w2c = inverse(c2w(quat,
+   *   trans)) and origin = trans of the pose as it stands when the iteration starts (slams/tracking.py:316-319) instead.
+   *   w_merge: dns_mlp_prepare image of Merge (merge_in = 3 merge_bins + map_c inputs in (64, 128], % 8 == 0; merge_out outputs
+   *   == hidden == 32), merge_bound [3][2].  n_views in [1, 8].  n_feat >= 2 hidden; code must be NULL. */
+  const float* maps;
+  const float* w2c;
+  const float* origin;
+  uint32_t follow_mask;
+  const float* w_merge;
+  uint32_t merge_in, merge_out, merge_bins;
+  const double* merge_bound;
+  uint32_t n_views, map_c;
+  int32_t map_h, map_w;
 } DnsTrackFused;
+uint64_t dns_track_fused_args_bytes(void);   /* sizeof(DnsTrackFused) as the library was built: callers check their own layout */
 uint64_t dns_track_fused_ws_floats(const DnsTrackFused* a);
 int dns_track_fused_begin(const int64_t* pix_all, uint32_t n_rays, uint32_t n_iters, const float* depth, int W, int H0, int W0,
                           int W1, float* t_surf_all, uint32_t n_surface, uint32_t* dmax_all, void* stream);
