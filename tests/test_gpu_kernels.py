@@ -10,7 +10,7 @@ import torch
 
 from oracle import render_math as rm
 from oracle import tcnn_ref as tr
-from util import assert_close, rel_err, table_level_groups, mlp_param_groups
+from util import REPORT, assert_close, rel_err, table_level_groups, mlp_param_groups
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -541,6 +541,7 @@ def test_raygen_sample_bit_exact_vs_oracle(nu, ns):
     outs = ops.raygen_sample(q.to(DEV), T.to(DEV), idx.to(DEV), color.to(DEV), depth.to(DEV), label.to(DEV), cam, bound,
                              (0, H, 0, W), npf, tu.to(DEV) if nu else None, t.to(DEV), t0.to(DEV))
     rays_o, rays_d, pts, gt_color, gt_depth, gt_label, inside, z = [o.cpu() for o in outs]
+    n_loose = 0                                                       # frames compared at rtol 1e-6 instead of bit for bit
     for f in range(K):
         sl = slice(f * npf, (f + 1) * npf)
         img5 = torch.cat((color[f], depth[f][..., None], label[f][..., None]), -1)
@@ -559,8 +560,12 @@ def test_raygen_sample_bit_exact_vs_oracle(nu, ns):
             assert torch.equal(z[sl], zo), f"frame {f}: z not bit-exact"
             assert torch.equal(pts[sl], rm.points_from_rays(ro, rd, zo))
         else:
+            # oracle/render_math.py sums in torch's association; the kernel's own is held bit for bit by test_gpu_raygen.py
+            n_loose += 1
             assert_close(z[sl], zo, rtol=1e-6, what="z")
         assert (z[sl][:, 1:] >= z[sl][:, :-1]).all()                  # sorted ascending
+    REPORT.append((f"raygen_sample {nu}+{ns} vs oracle: frames not bit-equal in rays_d (z held to 1e-6 only): {n_loose} of {K}",
+                   float(n_loose), 0.0, 1e-6))
 
 
 def test_sample_along_rays_golden_bit_exact(golden_dir):
