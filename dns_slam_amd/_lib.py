@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 class DnsGridMeta(C.Structure):
@@ -134,6 +134,9 @@ SIGNATURES = {
     "dns_keyframe_project": (C.c_int, [_P, _U, _P, _U, _P, _P, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
     "dns_mesh_cc_ws_bytes": (C.c_uint64, [_U]),
     "dns_mesh_components": (C.c_int, [_P, _U, _P, _U, _P, _P, _P, _P, _P]),
+    "dns_mesh_holes_ws_bytes": (C.c_uint64, [_U, _U]),
+    "dns_mesh_holes_count": (C.c_int, [_P, _U, _U, _U, _P, _P, _P]),
+    "dns_mesh_holes_emit": (C.c_int, [_P, _U, _U, _P, _P]),
     "dns_nearest_ws_bytes": (C.c_uint64, [_U, _U]),
     "dns_nearest_points": (C.c_int, [_P, _U, _P, _U, _U, _U, _P, _P, _P, _P, _P]),
     "dns_icp_ws_bytes": (C.c_uint64, [_U, _U]),

@@ -17,6 +17,10 @@ pass, marching cubes, cleaning and the component filter are the same with and wi
 ``Mesher.get_bound_from_frames`` is the reference's scene bound (meshing.py:380-445): the keyframes' depth images fused into a TSDF
 (csrc/tsdf.hip, ``ops.tsdf_fuse`` / ``ops.tsdf_vertices``), the convex hull of its vertices and the camera centres (csrc/hull.hip,
 ``ops.convex_hull``), scaled by ``clean_mesh_bound_scale``; ``bound_planes="frames"`` hands it to the forecast mesh's cleaning.
+
+``Mesher.fill_holes`` and the ``holes=`` keyword are the reference's ``mesh.fill_holes()`` (meshing.py:770, trimesh's
+``repair.fill_holes``; csrc/mesh_holes.hip, ``ops.mesh_fill_holes``): the boundary loops of three and four edges closed with faces
+wound against their neighbours, in an order that is a function of the mesh alone.
 """
 from __future__ import annotations
 
@@ -294,7 +298,7 @@ class Mesher:
 
     @torch.no_grad()
     def extract(self, keyframe_dict, stage="fine", clean_mesh=True, components=None, min_area=None, stem=None, *, forecast=False,
-                depth_test=False, all_frames=None, bound_planes=None):
+                depth_test=False, all_frames=None, bound_planes=None, holes=None):
         """-> (verts [V,3] fp32 world / scale, faces [F,3] int32, colors [V,3] uint8, labels [V] int64), all on the device.
         ``components``: None, "small" (keep the components whose area exceeds ``min_area``, default
         ``cfg['meshing']['remove_small_geometry_threshold'] * scale * scale``) or "largest" (meshing.py:721-733); the filter
@@ -309,8 +313,13 @@ class Mesher:
         ``scipy.spatial.ConvexHull(...).equations``, in the scaled units of the marching-cubes bound.  ``bound_planes="frames"`` is the
         reference's own bound, ``get_bound_from_frames(keyframe_dict).planes`` (a TSDF fusion of the keyframes and its scaled hull);
         it is never built unasked, so ``forecast`` with ``clean_mesh`` and no ``bound_planes`` is refused.  The vertices whose mask
-        is forecast are coloured (0, 255, 255) (:756-762)."""
+        is forecast are coloured (0, 255, 255) (:756-762).
+
+        ``holes``: None (no filling), True (= 4, the reference's ``mesh.fill_holes()``, meshing.py:770) or the largest boundary loop to
+        close, an int in 3 .. 32: the faces returned are ``fill_holes``' -- the cleaned and filtered faces first, the new ones after
+        them.  No vertex is added, so colours and labels are the same."""
         self._check_supported(stem)
+        holes = _holes_arg("Mesher.extract", holes)
         if forecast and clean_mesh and bound_planes is None:
             raise NotImplementedError("Mesher.extract: forecast=True with clean_mesh=True needs a bound: bound_planes=\"frames\" builds the "
                                       "reference's (Mesher.get_bound_from_frames), or pass the half-spaces [M,4] of a convex bound")
@@ -343,6 +352,8 @@ class Mesher:
         if forecast and verts.shape[0]:
             fore = self._classes(verts, self._mask_args(keyframe_dict, all_frames, depth_test)) == ops.MASK_FORECAST
             colors[fore] = torch.tensor([0, 255, 255], dtype=torch.uint8, device=colors.device)
+        if holes is not None:
+            faces = self.fill_holes(verts, faces, holes)[0]
         return verts / self.scale, faces, colors, labels
 
     def clean(self, verts, faces, kf, depth_test=False, mask_args=None):
@@ -376,6 +387,12 @@ class Mesher:
             keep = comp_area > float(min_area)
         return compact_mesh(verts, faces, keep)[:2]
 
+    def fill_holes(self, verts, faces, max_edges=4):
+        """meshing.py:770 on the device (ops.mesh_fill_holes): -> (faces_out [F + A, 3] int32, info).  The boundary loops of 3 ..
+        ``max_edges`` edges whose vertices all have one boundary edge in and one out get a fan from their smallest vertex, wound
+        against the faces across the boundary; ``faces`` come first, unchanged, and no vertex is added (include/dns_hip.h)."""
+        return ops.mesh_fill_holes(faces, int(verts.shape[0]), max_edges)
+
     def vertex_query(self, verts, kf, stage="fine", stem=None):
         """meshing.py:735-753: colours (clip(rgb, 0, 1) * 255 as uint8) and labels (argmax, -1 outside the bound) at the
         vertices, the > 1 point rule per points_batch_size chunk of vertices.  With ``stem`` (``kf`` from
@@ -396,14 +413,16 @@ class Mesher:
 
     def get_mesh(self, mesh_out_file, keyframe_dict, idx, color=True, label=False, palette=None, show_forecast=False,
                  element=False, clean_mesh=None, stage="fine", remove_small_geometry=False, fill_holes=False, components=None,
-                 min_area=None, stem=None, *, forecast=False, depth_test=False, all_frames=None, bound_planes=None):
+                 min_area=None, stem=None, *, forecast=False, depth_test=False, all_frames=None, bound_planes=None, holes=None):
         """Writes ``{mesh_out_file}/mesh_{idx}.ply`` (vertex colours when ``color``, the vertex labels as an int property) and,
         with ``label`` and a ``palette`` (class -> RGB: an [n_class, 3] array, a dict or a callable like the reference's
         v_map_function), ``mesh_{idx}_semantic.ply``.  Returns the paths written.  ``components`` / ``min_area``: the
         connected-components filter of ``extract`` (meshing.py:721-733); ``stem``, ``forecast`` (the reference's show_forecast),
-        ``depth_test``, ``all_frames`` and ``bound_planes`` ("frames" included): as in ``extract``.  fill_holes (meshing.py:770) is not implemented and,
-        like the reference's own spellings of the filters, of the forecast mesh and of the per-class meshes, refused when asked
-        for."""
+        ``depth_test``, ``all_frames`` and ``bound_planes`` ("frames" included): as in ``extract``.
+        ``holes``: None, True (= 4, the reference's ``mesh.fill_holes()``, meshing.py:770) or an int in 3 .. 32: ``mesh_{idx}.ply``
+        gets ``fill_holes``' face list; as in the reference (:781) the semantic mesh keeps the unfilled faces.  The reference's own
+        spellings -- of the filters, of the forecast mesh, of the per-class meshes and ``fill_holes`` -- are refused when asked for,
+        each naming ours."""
         if show_forecast:
             raise NotImplementedError("Mesher.get_mesh: show_forecast is not a keyword here; pass forecast=True (with "
                                       "bound_planes=\"frames\" when the mesh is cleaned)")
@@ -414,14 +433,17 @@ class Mesher:
             raise NotImplementedError("Mesher.get_mesh: remove_small_geometry is not a keyword here; pass components=\"small\" "
                                       "(or components=\"largest\")")
         if fill_holes:
-            raise NotImplementedError("Mesher.get_mesh: fill_holes is not supported")
+            raise NotImplementedError("Mesher.get_mesh: fill_holes is not a keyword here; pass holes=True (or the largest loop to "
+                                      "close, holes=3 .. 32)")
+        holes = _holes_arg("Mesher.get_mesh", holes)
         verts, faces, colors, labels = self.extract(keyframe_dict, stage, self.clean_mesh if clean_mesh is None else clean_mesh,
                                                     components, min_area, stem, forecast=forecast, depth_test=depth_test,
                                                     all_frames=all_frames, bound_planes=bound_planes)
         v, f, lab = verts.cpu().numpy(), faces.cpu().numpy(), labels.cpu().numpy()
+        filled = f if holes is None else self.fill_holes(verts, faces, holes)[0].cpu().numpy()
         os.makedirs(mesh_out_file, exist_ok=True)
         out = [os.path.join(mesh_out_file, f"mesh_{idx}.ply")]
-        write_ply(out[0], v, f, colors.cpu().numpy() if color else None, lab)
+        write_ply(out[0], v, filled, colors.cpu().numpy() if color else None, lab)
         if label and palette is not None:
             out.append(os.path.join(mesh_out_file, f"mesh_{idx}_semantic.ply"))
             write_ply(out[1], v, f, label_colors(lab, palette), lab)
@@ -443,6 +465,17 @@ class Mesher:
             write_ply(out[-1], v.cpu().numpy(), f.cpu().numpy(), colors[used].cpu().numpy() if color else None,
                       labels[used].cpu().numpy())
         return out
+
+
+def _holes_arg(who, holes):
+    """``holes`` of extract / get_mesh -> None or max_edges: True is 4 (trimesh.repair.fill_holes), an int is itself."""
+    if holes is None:
+        return None
+    if holes is True:
+        return ops.HOLES_MAX_EDGES
+    if isinstance(holes, bool) or not isinstance(holes, (int, np.integer)) or not 3 <= int(holes) <= 32:
+        raise ValueError(f"{who}: holes must be None, True or an int in 3 .. 32, got {holes!r}")
+    return int(holes)
 
 
 def inside_planes(points, planes):

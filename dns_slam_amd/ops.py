@@ -1330,6 +1330,60 @@ def mesh_components(verts: torch.Tensor, faces: torch.Tensor):
     return comp, comp_area, n_comp
 
 
+# ----------------------------------------------------------------------------- mesh holes (csrc/mesh_holes.hip)
+HOLES_INFO_KEYS = ("faces_added", "loops_filled", "boundary_edges", "nonmanifold_edges", "vertices_skipped", "degenerate",
+                   "bad_index")
+HOLES_MAX_EDGES = 4                        # trimesh.repair.fill_holes closes loops of three and four edges
+
+
+def mesh_fill_holes(faces: torch.Tensor, n_verts: int, max_edges: int = HOLES_MAX_EDGES):
+    """faces [F,3] int32 over ``n_verts`` vertices -> (faces_out [F + A, 3] int32: the input faces, unchanged, then the A faces
+    that close the boundary loops of 3 .. ``max_edges`` edges, info: a dict of ints with ``HOLES_INFO_KEYS`` plus ``watertight``,
+    true iff the INPUT has no boundary and no non-manifold edge).  mesh.fill_holes() of meshing.py:770 under the definition of
+    include/dns_hip.h: every added face starts with its loop's smallest vertex, loops in ascending order of it, a loop's faces in
+    fan order; loops through a vertex with more than one boundary edge in or out are left open and their vertices counted in
+    ``vertices_skipped``.  ``max_edges`` in 3 .. 32.  A vertex index outside [0, n_verts) raises ValueError.  One host read (the
+    whole of info, the total included)."""
+    if not isinstance(faces, torch.Tensor):
+        raise ValueError(f"mesh_fill_holes: faces must be a tensor, got {type(faces).__name__}")
+    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 3 <= int(max_edges) <= 32:
+        raise ValueError(f"mesh_fill_holes: max_edges must be an int in 3 .. 32, got {max_edges!r}")
+    if isinstance(n_verts, bool) or not isinstance(n_verts, (int, np.integer)) or not 0 <= int(n_verts) < 2 ** 31:
+        raise ValueError(f"mesh_fill_holes: n_verts must be an int in [0, 2^31), got {n_verts!r}")
+    f = faces.detach().contiguous()
+    require_cuda(f)
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"mesh_fill_holes: faces [F,3], got {tuple(f.shape)}")
+    if f.dtype != torch.int32:
+        raise ValueError(f"mesh_fill_holes: faces must be int32, got {f.dtype}")
+    V, F, max_edges = int(n_verts), int(f.shape[0]), int(max_edges)
+    if F == 0:
+        info = {k: 0 for k in HOLES_INFO_KEYS}
+        info["watertight"] = True
+        return faces, info
+    dev = f.device
+    ws_b = int(_rawlib.dns_mesh_holes_ws_bytes(F, V))
+    if ws_b == 0:
+        raise ValueError(f"mesh_fill_holes: {F} faces are too many (>= 2^29)")
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    info_d = torch.empty(8, dtype=torch.int32, device=dev)
+    check(lib.dns_mesh_holes_count(ptr(f), F, V, max_edges, ptr(ws), ptr(info_d), stream_ptr()), "dns_mesh_holes_count")
+    words = [int(x) for x in info_d.cpu().tolist()]
+    if words[6]:
+        raise ValueError(f"mesh_fill_holes: a face holds a vertex index outside [0, {V})")
+    if words[7]:
+        raise ValueError("mesh_fill_holes: edge table overflow")
+    info = dict(zip(HOLES_INFO_KEYS, words))
+    info["watertight"] = info["boundary_edges"] == 0 and info["nonmanifold_edges"] == 0
+    A = info["faces_added"]
+    if A == 0:
+        return f, info
+    out = torch.empty(F + A, 3, dtype=torch.int32, device=dev)
+    out[:F] = f
+    check(lib.dns_mesh_holes_emit(ptr(ws), V, max_edges, ptr(out[F:]), stream_ptr()), "dns_mesh_holes_emit")
+    return out, info
+
+
 # ----------------------------------------------------------------------------- mesh evaluation (csrc/mesh_eval.hip)
 NEAREST_MAX_RINGS = 8
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 25
+#define DNS_ABI_VERSION 26
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -668,6 +668,45 @@ int dns_keyframe_project(const float* pts, uint32_t P, const float* w2c, uint32_
 uint64_t dns_mesh_cc_ws_bytes(uint32_t F);
 int dns_mesh_components(const float* verts, uint32_t V, const int32_t* faces, uint32_t F, void* ws, int32_t* comp, double* comp_area,
                         uint32_t* status, void* stream);
+
+/* ---- mesh holes (mesh.fill_holes() of slams/meshing.py:770, i.e. trimesh.repair.fill_holes; csrc/mesh_holes.hip; ABI v26) ------
+ * Closes the small boundary loops of a triangle list faces [F,3] int32 over V vertices with new faces; no vertex is added and the
+ * input faces are not touched.  The definition:
+ *   - An undirected edge (min(a,b), max(a,b)) that exactly one of the 3F face edges holds is a boundary edge, directed a -> b as
+ *     its face winds it.  A face edge with a == b is not an edge (it is counted in `degenerate`); an edge with three or more
+ *     holders is non-manifold (counted) and not boundary.
+ *   - A vertex is SIMPLE iff exactly one boundary edge leaves it and exactly one enters it.  A loop is filled iff all its vertices
+ *     are simple and it has 3 .. max_edges edges.  Loops through a non-simple vertex -- two holes touching in a vertex,
+ *     inconsistent winding, non-manifold neighbourhoods -- are not filled; the boundary vertices that are not simple are counted
+ *     in `vertices_skipped`.  (trimesh's outcome there depends on networkx's traversal order.)
+ *   - The loop v0 -> v1 -> ... -> v_{L-1} -> v0, v0 its SMALLEST vertex index, gets the fan (v0, v_{i+1}, v_i), i = 1 .. L-2:
+ *     L = 3 gives (v0, v2, v1), L = 4 gives (v0, v2, v1), (v0, v3, v2).  Every new face reverses the boundary half-edges it
+ *     closes (trimesh's winding rule); the quad's diagonal starts at the loop's smallest vertex (trimesh's depends on networkx's
+ *     traversal order).  A lone triangle gets its mirror face, as in trimesh.
+ *   - Loops come in ascending order of v0, a loop's faces in fan order.
+ * The added block is therefore a function of the mesh alone: the same bits from call to call, and under any permutation of the
+ * input faces and any rotation of a face's three indices.
+ *   dns_mesh_holes_ws_bytes: bytes of workspace for F faces over V vertices (four words per vertex, the scan's carries and a
+ *     4F-slot edge table of 16 bytes per slot); 0: refused size (F = 0 needs none; F >= 2^29 and V >= 2^31 are refused).
+ *   dns_mesh_holes_count: everything but the new faces.  max_edges in 3 .. 32.  info [DNS_HOLES_INFO_WORDS] uint32 (device), for
+ *     the caller to read back: the counters below, all integer sums and so the same for every call.  A vertex index outside
+ *     [0, V) is never dereferenced: it sets info[BAD_INDEX], its face contributes nothing, and the caller must treat the result
+ *     as invalid.  info[TABLE_FULL] is 0 (4F slots hold 3F keys; checked rather than assumed).  F = 0: info is zeroed.
+ *   dns_mesh_holes_emit: new_faces [info[FACES_ADDED], 3] int32 from the workspace dns_mesh_holes_count left, with the same V and
+ *     max_edges.  Every store is below the 3 info[FACES_ADDED] words the caller sized new_faces by.  The caller skips the call
+ *     where info[FACES_ADDED] is 0. */
+#define DNS_HOLES_INFO_FACES_ADDED 0
+#define DNS_HOLES_INFO_LOOPS_FILLED 1
+#define DNS_HOLES_INFO_BOUNDARY_EDGES 2        /* before filling */
+#define DNS_HOLES_INFO_NONMANIFOLD_EDGES 3
+#define DNS_HOLES_INFO_VERTICES_SKIPPED 4
+#define DNS_HOLES_INFO_DEGENERATE 5
+#define DNS_HOLES_INFO_BAD_INDEX 6
+#define DNS_HOLES_INFO_TABLE_FULL 7
+#define DNS_HOLES_INFO_WORDS 8
+uint64_t dns_mesh_holes_ws_bytes(uint32_t F, uint32_t V);
+int dns_mesh_holes_count(const int32_t* faces, uint32_t F, uint32_t V, uint32_t max_edges, void* ws, uint32_t* info, void* stream);
+int dns_mesh_holes_emit(const void* ws, uint32_t V, uint32_t max_edges, int32_t* new_faces, void* stream);
 
 /* ---- mesh evaluation (eval_3d.py, cull_mesh.py of the reference; csrc/mesh_eval.hip; ABI v15, v16) ---------------------------
  * dns_nearest_points: for each of N queries query [N,3] fp32 the Euclidean distance dist [N] fp32 to the nearest of M reference
