@@ -110,12 +110,18 @@ __device__ __forceinline__ float2 grid_level(const float2* __restrict__ table, c
   return make_float2(a0, a1);
 }
 
+// A non-finite coordinate must not leave as a finite row or gradient: fminf / fmaxf drop a NaN, so the clamp alone turned a NaN
+// or +-Inf distance (r = NaN either way: Inf - Inf) into 0 and every such axis into the finite row (0, ..., 0, 1); the pdf's
+// support test did the same to +-Inf.  The distance is what is tested, not r: r is also NaN at FINITE distances beyond ~4.3e9
+// bins (u4 overflows), where the clamp's 0 is harmless (all three images saturate alike) and stays as it was -- for every
+// finite coordinate the bits are unchanged.
 __device__ __forceinline__ float quartic_cdf(float v, float n) {
 #pragma clang fp contract(off)
   const float u = v * n;
   const float u2 = u * u;
   const float u4 = u2 * u2;
   const float r = (15.0f / 16.0f) * u * (1.0f - (2.0f / 3.0f) * u2 + (1.0f / 5.0f) * u4) + 0.5f;
+  if (!(fabsf(v) < INFINITY)) return v - v;               // NaN
   return fminf(fmaxf(r, 0.0f), 1.0f);
 }
 
@@ -123,6 +129,7 @@ __device__ __forceinline__ float quartic_pdf(float v, float n) {
 #pragma clang fp contract(off)
   const float u = v * n;
   const float u2 = u * u;
+  if (!(fabsf(v) < INFINITY)) return v - v;               // NaN (see quartic_cdf)
   if (u2 > 1.0f) return 0.0f;
   const float t = 1.0f - u2;
   return (15.0f / 16.0f) * n * t * t;
