@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 class DnsGridMeta(C.Structure):
@@ -152,6 +152,9 @@ SIGNATURES = {
                                       _P, _P]),
     "dns_depth_l1": (C.c_int, [_P, _P, _U, _U, _U, _P, _P, _P]),
     "dns_views_see_any": (C.c_int, [_P, _U, _P, _U, _I, _I, C.POINTER(C.c_float), _P, _P]),
+    "dns_render_mesh_ws_bytes": (C.c_uint64, [_U, _U, _U, _U]),
+    "dns_render_mesh": (C.c_int, [_P, _U, _P, _U, _P, _P, _P, _U, _U, _P, _U, _U, _U, C.POINTER(C.c_float), C.c_float, C.c_float, _U,
+                                  C.c_float, C.POINTER(C.c_float), _U, _P, _P, _P, _P, _P, _P]),
     "dns_kf_pair_count": (C.c_int, [_P, _U, _P, _U, _P, _I, _I, C.POINTER(C.c_float), _P, _P]),
     "dns_kf_pair_emit": (C.c_int, [_P, _U, _P, _U, _P, _I, _I, C.POINTER(C.c_float), _P, _P, C.c_uint64, _P]),
     "dns_kf_pair_rows": (C.c_int, [_P, C.c_uint64, _P, _U, _P, _U, _P, _U, _I, _I, _I, _I, _P, _P, _U, _P]),

@@ -18,6 +18,7 @@
 //                   does not depend on the order: the image is the same bits for every call and both methods.
 // A triangle with a non-finite vertex (world or camera space) is skipped and flagged; one with n = 0 is skipped.
 //
+// The set-up and the per-pixel expressions are dev_raster.hpp's, shared with the colour rasteriser (mesh_render.hip).
 //   rs_init:    the image set to +inf, the list counters and the status words cleared.
 //   rs_setup:   thread = (triangle, view).  Camera space, normal, edge vectors; culled when wholly nearer than z_near, beyond
 //               z_far or outside one of the four side planes of the image (tested as half-spaces of camera space, with a pixel
@@ -38,116 +39,19 @@
 #include <algorithm>
 #include "common.hpp"
 #include "dev_project.hpp"
+#include "dev_raster.hpp"
 #include "dev_reduce.hpp"
 
 namespace dns {
 
 namespace {
 
-constexpr int RS_BLOCK = 256;
-constexpr int RS_SMALL = 8;                                      // side of the largest box a set-up thread draws itself
-constexpr uint32_t RS_LIST_CAP = 1u << 24;                       // (triangle, view) pairs per launch = list entries (128 MiB)
-constexpr uint32_t RS_MAX_LAUNCHES = 65536;                      // list counters in the workspace
-constexpr uint32_t RS_LARGE_GRID = 2048;
 constexpr uint32_t RS_INF = 0x7f800000u;
-
-struct RsCam {
-  float fx, fy, cx, cy, z_near, z_far;
-  int H, W;
-};
-
-struct RsTri {
-  float c[3][3];                                                 // signed edge vectors
-  float n[3], num;
-  int x0, x1, y0, y1;                                            // pixel box, inclusive
-};
-
-__device__ __forceinline__ void rs_cross(const float* a, const float* b, float* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// The set-up of triangle f under the pose m (16 floats): false when there is nothing to draw.
-__device__ __forceinline__ bool rs_setup(const float* __restrict__ verts, uint32_t P, const int32_t* __restrict__ faces, uint32_t f,
-                                         const float* __restrict__ m, const RsCam& cam, RsTri& t, uint32_t* __restrict__ status) {
-  const uint32_t id[3] = {(uint32_t)faces[3 * (size_t)f], (uint32_t)faces[3 * (size_t)f + 1], (uint32_t)faces[3 * (size_t)f + 2]};
-  if (id[0] >= P || id[1] >= P || id[2] >= P) {                   // never dereferenced; the ops wrapper refuses such a mesh
-    atomicOr(&status[0], DNS_RASTER_BAD_INDEX);
-    return false;
-  }
-  float v[3][3];
-  bool finite = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float x = verts[3 * (size_t)id[k]], y = verts[3 * (size_t)id[k] + 1], z = verts[3 * (size_t)id[k] + 2];
-    finite = finite && isfinite(x) && isfinite(y) && isfinite(z);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      v[k][r] = ((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3];
-      finite = finite && isfinite(v[k][r]);
-    }
-  }
-  if (!finite) {
-    atomicOr(&status[0], DNS_RASTER_NONFINITE);
-    return false;
-  }
-  const float e1[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]};
-  const float e2[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
-  rs_cross(e1, e2, t.n);
-  if (t.n[0] == 0.f && t.n[1] == 0.f && t.n[2] == 0.f) return false;
-  t.num = (t.n[0] * v[0][0] + t.n[1] * v[0][1]) + t.n[2] * v[0][2];
-  const float zmin = fminf(fminf(v[0][2], v[1][2]), v[2][2]), zmax = fmaxf(fmaxf(v[0][2], v[1][2]), v[2][2]);
-  if (zmax < cam.z_near || zmin > cam.z_far) return false;
-  // side planes with a pixel of slack: u = fx x / z + cx < -1 (left) or > W (right) for z > 0 are the half-spaces
-  // fx x + (cx + 1) z < 0 and fx x + (cx - W) z > 0; a triangle wholly inside one has no visible point in the image
-  const float fW = (float)cam.W, fH = (float)cam.H;
-  bool left = true, right = true, top = true, bottom = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float ax = cam.fx * v[k][0], ay = cam.fy * v[k][1], z = v[k][2];
-    left = left && ax + (cam.cx + 1.f) * z < 0.f;
-    right = right && ax + (cam.cx - fW) * z > 0.f;
-    top = top && ay + (cam.cy + 1.f) * z < 0.f;
-    bottom = bottom && ay + (cam.cy - fH) * z > 0.f;
-  }
-  if (left || right || top || bottom) return false;
-  if (zmin >= cam.z_near) {
-    float ulo = __builtin_inff(), uhi = -__builtin_inff(), vlo = ulo, vhi = uhi;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float u = cam.fx * (v[k][0] / v[k][2]) + cam.cx, w = cam.fy * (v[k][1] / v[k][2]) + cam.cy;
-      ulo = fminf(ulo, u), uhi = fmaxf(uhi, u), vlo = fminf(vlo, w), vhi = fmaxf(vhi, w);
-    }
-    // clamped as floats first (a quotient may be huge or, overflowed, infinite); NaN cannot occur: the vertices are finite, z > 0
-    t.x0 = (int)fminf(fmaxf(floorf(ulo) - 1.f, 0.f), fW);
-    t.x1 = (int)fminf(fmaxf(ceilf(uhi) + 1.f, -1.f), fW - 1.f);
-    t.y0 = (int)fminf(fmaxf(floorf(vlo) - 1.f, 0.f), fH);
-    t.y1 = (int)fminf(fmaxf(ceilf(vhi) + 1.f, -1.f), fH - 1.f);
-    if (t.x0 > t.x1 || t.y0 > t.y1) return false;
-  } else {
-    t.x0 = 0, t.x1 = cam.W - 1, t.y0 = 0, t.y1 = cam.H - 1;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int a = k, b = (k + 1) % 3;
-    const bool swap = id[a] > id[b];                              // equal indices: n = 0, not reached
-    rs_cross(v[swap ? b : a], v[swap ? a : b], t.c[k]);
-    if (swap) t.c[k][0] = -t.c[k][0], t.c[k][1] = -t.c[k][1], t.c[k][2] = -t.c[k][2];
-  }
-  return true;
-}
 
 // Pixel (row i, column j) of the image img [H,W]; 0 <= i < H and 0 <= j < W by the caller's box.
 __device__ __forceinline__ void rs_pixel(const RsTri& t, const RsCam& cam, int i, int j, uint32_t* __restrict__ img) {
-  const float dx = ((float)j - cam.cx) / cam.fx, dy = ((float)i - cam.cy) / cam.fy;
-  const float E0 = (dx * t.c[0][0] + dy * t.c[0][1]) + t.c[0][2];
-  const float E1 = (dx * t.c[1][0] + dy * t.c[1][1]) + t.c[1][2];
-  const float E2 = (dx * t.c[2][0] + dy * t.c[2][1]) + t.c[2][2];
-  if (!((E0 >= 0.f && E1 >= 0.f && E2 >= 0.f) || (E0 <= 0.f && E1 <= 0.f && E2 <= 0.f))) return;
-  const float den = (t.n[0] * dx + t.n[1] * dy) + t.n[2];
-  const float d = t.num / den;
-  if (d >= cam.z_near && d <= cam.z_far) {                        // false for NaN; d > 0: its bits order as the value
+  float d;
+  if (rs_depth(t, cam, i, j, d)) {
     uint32_t* p = img + (size_t)i * (size_t)cam.W + (size_t)j;
     const uint32_t bits = __float_as_uint(d);
     if (bits < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, bits);
@@ -285,14 +189,6 @@ __global__ __launch_bounds__(VS_BLOCK) void views_see_any_kernel(const float* __
 }  // namespace dns
 
 using namespace dns;
-
-namespace {
-
-inline uint64_t rs_list_entries(uint32_t F, uint32_t V, uint32_t cap) {
-  return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)F * V, cap));
-}
-
-}  // namespace
 
 extern "C" uint64_t dns_rasterize_ws_bytes(uint32_t F, uint32_t V, uint32_t H, uint32_t W) {
   if (F >= (1u << 31) || H == 0 || W == 0 || H > 32768u || W > 32768u) return 0;

@@ -1769,6 +1769,107 @@ def views_see_any(points: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: f
     return sees.bool()
 
 
+# ----------------------------------------------------------------------------- headless visualiser (csrc/mesh_render.hip)
+RENDER_CULL = (None, "back", "front")
+RENDER_SHADE = (None, "headlight")
+RENDER_MAX_POINT_SIZE = 16
+_RENDER_CULL_FLAGS = {None: 0, "back": 4, "front": 8}          # DNS_RENDER_CULL_BACK, DNS_RENDER_CULL_FRONT
+_RENDER_HEADLIGHT = 16                                         # DNS_RENDER_HEADLIGHT
+
+
+def _render_colors(who, what, colors, n, dev):
+    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32 or tuple(colors.shape) != (n, 3):
+        got = (tuple(colors.shape), colors.dtype) if isinstance(colors, torch.Tensor) else type(colors).__name__
+        raise ValueError(f"{who}: {what} must be a fp32 tensor [{n},3], got {got}")
+    c = colors.detach().contiguous()
+    require_cuda(c)
+    return c
+
+
+def render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, *, z_near=0.01, z_far=20.0, cull=None, shade=None,
+                       ambient=0.3, background=(1, 1, 1), points=None, point_colors=None, point_size=4, method="auto",
+                       list_cap=None, stats=False):
+    """``render_mesh`` without its host read: the face indices are NOT validated (a face with an index outside [0, P) is skipped
+    by the kernel and flagged in status[0] bit 1); int64 faces must fit int32."""
+    who = "render_mesh"
+    v, f, w = _raster_arguments(verts, faces, w2c, H, W, method)
+    f = f.to(torch.int32)
+    zn, zf = float(z_near), float(z_far)
+    if not (zn > 0.0 and zf >= zn and math.isfinite(zf)):
+        raise ValueError(f"{who}: need 0 < z_near <= z_far < inf, got {z_near!r}, {z_far!r}")
+    if not (all(math.isfinite(float(x)) for x in (fx, fy, cx, cy)) and float(fx) != 0.0 and float(fy) != 0.0):
+        raise ValueError(f"{who}: the intrinsics must be finite, fx and fy non-zero")
+    if cull not in RENDER_CULL:
+        raise ValueError(f"{who}: cull must be one of {RENDER_CULL}, got {cull!r}")
+    if shade not in RENDER_SHADE:
+        raise ValueError(f"{who}: shade must be one of {RENDER_SHADE}, got {shade!r}")
+    amb = float(ambient)
+    if not 0.0 <= amb <= 1.0:
+        raise ValueError(f"{who}: ambient must be in [0, 1], got {ambient!r}")
+    if isinstance(point_size, bool) or int(point_size) != point_size or not 1 <= int(point_size) <= RENDER_MAX_POINT_SIZE:
+        raise ValueError(f"{who}: point_size must be an integer in 1..{RENDER_MAX_POINT_SIZE}, got {point_size!r}")
+    bg = tuple(float(x) for x in background)
+    if len(bg) != 3 or not all(math.isfinite(x) for x in bg):
+        raise ValueError(f"{who}: background must be three finite numbers, got {background!r}")
+    P, F, V = int(v.shape[0]), int(f.shape[0]), int(w.shape[0])
+    dev = v.device
+    col = _render_colors(who, "colors", colors, P, dev)
+    if (points is None) != (point_colors is None):
+        raise ValueError(f"{who}: points and point_colors come together")
+    pts = pcol = None
+    N = 0
+    if points is not None:
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"{who}: points must be a tensor [N,3]")
+        pts = points.detach().contiguous().float()
+        require_cuda(pts)
+        N = int(pts.shape[0])
+        pcol = _render_colors(who, "point_colors", point_colors, N, dev)
+    H, W = int(H), int(W)
+    out = {"color": torch.empty(V, H, W, 3, dtype=torch.float32, device=dev),
+           "depth": torch.empty(V, H, W, dtype=torch.float32, device=dev),
+           "index": torch.empty(V, H, W, dtype=torch.int32, device=dev),
+           "status": torch.zeros(4, dtype=torch.int32, device=dev)}
+    if V == 0:
+        return out
+    ws_b = int(_rawlib.dns_render_mesh_ws_bytes(F, V, H, W))
+    if ws_b == 0:
+        raise ValueError(f"{who}: {F} faces at {H} x {W} are refused (F >= 2^31)")
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    flags = (1 if method == "simple" else 0) | (2 if stats else 0) | _RENDER_CULL_FLAGS[cull] | (_RENDER_HEADLIGHT if shade else 0)
+    check(lib.dns_render_mesh(ptr(v), P, ptr(f), F, ptr(col), ptr(pts), ptr(pcol), N, int(point_size), ptr(w), V, H, W,
+                              _intrinsics(fx, fy, cx, cy), zn, zf, flags, amb, (C.c_float * 3)(*bg), int(list_cap or 0), ptr(ws),
+                              ptr(out["color"]), ptr(out["depth"]), ptr(out["index"]), ptr(out["status"]), stream_ptr()),
+          "dns_render_mesh")
+    return out
+
+
+def render_mesh(verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: float,
+                fy: float, cx: float, cy: float, *, z_near: float = 0.01, z_far: float = 20.0, cull: Optional[str] = None,
+                shade: Optional[str] = None, ambient: float = 0.3, background=(1, 1, 1), points: Optional[torch.Tensor] = None,
+                point_colors: Optional[torch.Tensor] = None, point_size: int = 4, method: str = "auto",
+                list_cap: Optional[int] = None, stats: bool = False):
+    """Colour images of a triangle mesh with vertex colours and of a point cloud: verts [P,3] fp32, faces [F,3] int32, colors
+    [P,3] fp32, w2c [V,4,4] (``rasterize_depth``'s convention and arguments) -> {"color" [V,H,W,3] fp32, "depth" [V,H,W] fp32,
+    "index" [V,H,W] int32, "status" [4] int32}, device tensors.  ``index`` is the face seen through the pixel centre, -1 for the
+    background and -2 - k for point k; ``depth`` is ``rasterize_depth``'s image bit for bit when nothing is culled and there are
+    no points.  The nearest surface wins; at equal depth the lower face index, and a triangle before a point: the images are the
+    same bits for every call, both methods and every ``list_cap``.  Colours are interpolated perspective-correctly.
+    ``cull``: None, "back" or "front" -- a face is front-facing when the normal of its winding points at the camera.
+    ``shade``: None or "headlight" (colour times ambient + (1 - ambient) |cos| of the angle between the face normal and the pixel
+    ray: flat and two-sided).  ``points`` [N,3] with ``point_colors`` [N,3] fp32 are squares of ``point_size`` (1..16) pixels,
+    depth-tested against the mesh and each other, never shaded.  ``status``: [0] bit 0 a triangle with a non-finite vertex was
+    skipped, bit 2 a non-finite point was; [1] (triangle, view) pairs drawn through the list; [2] pairs drawn by their set-up
+    thread (with ``stats``).  The arithmetic is written out in include/dns_hip.h.  A face index outside [0, P), CPU tensors,
+    colours that are not fp32 [P,3] / [N,3], an unknown ``cull``, ``shade`` or ``method``, ``point_size`` outside 1..16 and
+    ``ambient`` outside [0, 1] raise ValueError (one host read for the indices)."""
+    v, f, _ = _raster_arguments(verts, faces, w2c, H, W, method)
+    _check_face_indices(f, int(v.shape[0]))
+    return render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, z_near=z_near, z_far=z_far, cull=cull, shade=shade,
+                              ambient=ambient, background=background, points=points, point_colors=point_colors,
+                              point_size=point_size, method=method, list_cap=list_cap, stats=stats)
+
+
 # ----------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)
 TSDF_UNIT = 16
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 26
+#define DNS_ABI_VERSION 27
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -853,6 +853,46 @@ int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t* faces, ui
 int dns_depth_l1(const float* a, const float* b, uint32_t V, uint32_t H, uint32_t W, double* partial, double* err, void* stream);
 int dns_views_see_any(const float* pts, uint32_t N, const float* w2c, uint32_t K, int H, int W, const float* intr, uint8_t* sees,
                       void* stream);
+
+/* ---- Headless visualiser (utils/viz.py:45-177 of the reference; csrc/mesh_render.hip; ABI v27) ----------------------------------
+ * dns_render_mesh: colour [V,H,W,3] fp32, depth [V,H,W] fp32 and index [V,H,W] int32 of the mesh verts [P,3], faces [F,3] int32,
+ * colors [P,3] fp32 (per vertex) and of the points [N,3] fp32 with point_colors [N,3] fp32, drawn as squares of point_size
+ * (1..16) pixels, seen from the V poses w2c [V,16]; intr, z_near, z_far, list_cap, the status words, DNS_RASTER_SIMPLE and
+ * DNS_RASTER_STATS as for dns_rasterize_depth.  Triangle set-up, coverage, depth, the skipped triangles and their flags are that
+ * function's expressions (csrc/dev_raster.hpp), so with N = 0 and no culling `depth` is dns_rasterize_depth's image bit for bit.
+ *   visibility: per pixel the minimum of the 64-bit keys (bits of the depth << 32) | id over everything that covers it, id = the
+ *     face index for a triangle and 0x80000000 | point index for a point: the nearest surface; at equal depth the lower face
+ *     index, and a triangle before a point.  The images are the same bits for every call, both methods and every list_cap.
+ *   culling, per (face, view), by num = (n.x v0.x + n.y v0.y) + n.z v0.z of the set-up: num < 0 is front-facing (the normal of
+ *     the winding points at the camera).  DNS_RENDER_CULL_BACK drops the faces with num > 0, DNS_RENDER_CULL_FRONT those with
+ *     num < 0; either drops num == 0.  Setting both is refused.
+ *   points, every operation one fp32 rounding: p = ((r0 x + r1 y) + r2 z) + t per row; skipped and flagged
+ *     (DNS_RENDER_NONFINITE_POINT) when the point or p is not finite; accepted iff z_near <= p.z <= z_far;
+ *     u = fx (p.x / p.z) + cx, w = fy (p.y / p.z) + cy, h = point_size * 0.5; the square is the columns ceil(u - h) ..
+ *     ceil(u - h) + point_size - 1 and the rows ceil(w - h) .. ceil(w - h) + point_size - 1 (the pixel centres in
+ *     [u - h, u + h)), clipped to the image; its key depth is p.z.
+ *   shading, one thread per pixel, every operation one fp32 rounding in this order:
+ *     background (no key): color = background [3 host floats], depth 0, index -1;
+ *     point: color = point_colors[point], depth = p.z, index = -2 - point;
+ *     face f: index = f, depth = t; with d, E0, E1, E2 (edges (0,1), (1,2), (2,0)) and den = (n.x d.x + n.y d.y) + n.z as
+ *       above: the three edge vectors sum to n, so den is the sum of the edge functions, and the weights divide by that sum
+ *       of the rounded E, S = (E0 + E1) + E2, which keeps them a partition of one: the perspective-correct weights are
+ *       w0 = E1 / S, w1 = E2 / S, w2 = E0 / S ((1, 0, 0) when S == 0: all three E are 0, the triangle is seen edge-on) and
+ *       per channel color = (w0 c0 + w1 c1) + w2 c2, c_k = colors[faces[f][k]];
+ *       with DNS_RENDER_HEADLIGHT: nn = (n.x n.x + n.y n.y) + n.z n.z, dd = (d.x d.x + d.y d.y) + 1,
+ *       light = ambient + (1 - ambient) * (|den| / (sqrt(nn) * sqrt(dd))), color = color * light (flat, two-sided; points are
+ *       not shaded).  0 <= ambient <= 1.
+ *   dns_render_mesh_ws_bytes: the keys (8 bytes per pixel and view), the list counters and the list (0: refused size).
+ * V = 0: nothing is launched.  F = 0 and N = 0: the background everywhere. */
+#define DNS_RENDER_CULL_BACK 4u
+#define DNS_RENDER_CULL_FRONT 8u
+#define DNS_RENDER_HEADLIGHT 16u
+#define DNS_RENDER_NONFINITE_POINT 4u
+uint64_t dns_render_mesh_ws_bytes(uint32_t F, uint32_t V, uint32_t H, uint32_t W);
+int dns_render_mesh(const float* verts, uint32_t P, const int32_t* faces, uint32_t F, const float* colors, const float* points,
+                    const float* point_colors, uint32_t N, uint32_t point_size, const float* w2c, uint32_t V, uint32_t H, uint32_t W,
+                    const float* intr, float z_near, float z_far, uint32_t flags, float ambient, const float* background,
+                    uint32_t list_cap, void* ws, float* color, float* depth, int32_t* index, uint32_t* status, void* stream);
 
 /* ---- keyframe codes of the mesh vertex query (get_2d_feature, slams/meshing.py:311-377; csrc/mesh_feature.hip; ABI v19) -------
  * For points pts [P,3] fp32 and K keyframes (w2c [K,16] fp32 row-major = torch.inverse(est_c2w), depth [K,H,W] fp32 = gt_depth,
