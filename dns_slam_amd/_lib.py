@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 
 class DnsGridMeta(C.Structure):
@@ -26,6 +26,11 @@ class DnsGridMeta(C.Structure):
 
 class DnsSplitRows(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("exps", C.c_void_p), ("ld", C.c_uint32), ("lo_off", C.c_uint32)]
+
+
+class DnsFramePrepDims(C.Structure):
+    """include/dns_hip.h: the image sizes of dns_prepare_frames' stages."""
+    _fields_ = [(k, C.c_uint32) for k in ("Hc", "Wc", "Hd", "Wd", "Hl", "Wl", "Hs", "Ws", "edge")]
 
 
 class DnsAdamTensor(C.Structure):
@@ -180,6 +185,11 @@ SIGNATURES = {
     "dns_lpips_head_blocks": (_U, [_U, _U]),
     "dns_lpips_head": (C.c_int, [_P, _P, _P, _U, _U, _U, _U, _P, _P]),
     "dns_lpips_finish": (C.c_int, [C.POINTER(_P), C.POINTER(_U), C.POINTER(_U), _U, _U, _P, _P, _P]),
+    "dns_frame_prep_table_words": (C.c_uint64, [C.POINTER(DnsFramePrepDims)]),
+    "dns_frame_prep_tables": (C.c_int, [C.POINTER(DnsFramePrepDims), _P, C.c_uint64]),
+    "dns_prepare_frames": (C.c_int, [_P, _I, _P, _P, _I, _P, C.POINTER(DnsFramePrepDims), _P, C.c_uint64, _U, C.c_float, C.c_float,
+                                     _P, _P, _P, _P]),
+    "dns_label_first_seen": (C.c_int, [_P, _I, C.c_uint64, _P, _P]),
 }
 
 

@@ -2429,3 +2429,209 @@ def lpips(pred: torch.Tensor, gt: torch.Tensor, weights: LpipsWeights, method: O
     if single:
         val, layers = val[0], layers[0]
     return {"lpips": val, "layers": layers}
+
+
+# ----------------------------------------------------------------------------- frame preparation (csrc/frame_prep.hip, csrc/frame_prep_plan.hpp)
+PREPARE_FRAMES_METHODS = ("kernel", "torch")
+PREPARE_FRAMES_DEFAULT = "kernel"
+LABEL_VALUES = 65536                         # entries of a label look-up table and of label_first_seen's result
+
+
+class FramePrepTables:
+    """The resampling tables of ``prepare_frames`` for one set of image sizes (include/dns_hip.h, "frame preparation"): built on the
+    host by the library (``dns_frame_prep_tables``), copied to ``device`` once.  ``words``: the host blob (int32 numpy);
+    ``dev``: its copy on the device; ``H``, ``W``: the size of a prepared frame."""
+
+    def __init__(self, color_hw, depth_hw, label_hw=None, crop_size=None, crop_edge=0, device="cuda"):
+        from ._lib import DnsFramePrepDims
+        pair = lambda v, what: self._pair(v, what)
+        self.color_hw, self.depth_hw = pair(color_hw, "color_hw"), pair(depth_hw, "depth_hw")
+        self.label_hw = None if label_hw is None else pair(label_hw, "label_hw")
+        self.crop_size = None if crop_size is None else pair(crop_size, "crop_size")
+        self.edge = int(crop_edge)
+        if self.edge < 0:
+            raise ValueError(f"frame_prep_tables: crop_edge {crop_edge}")
+        self.stage_hw = self.crop_size or self.depth_hw
+        lh, lw = self.label_hw or (0, 0)
+        self.dims = DnsFramePrepDims(*self.color_hw, *self.depth_hw, lh, lw, *self.stage_hw, self.edge)
+        n = int(_rawlib.dns_frame_prep_table_words(C.byref(self.dims)))
+        if n == 0:
+            raise ValueError(f"frame_prep_tables: sizes refused: colour {self.color_hw}, depth {self.depth_hw}, labels {self.label_hw}, "
+                             f"crop_size {self.crop_size}, crop_edge {self.edge} (sides 1..32768, 2 crop_edge below both output sides)")
+        self.words = np.empty(n, dtype=np.int32)
+        check(_rawlib.dns_frame_prep_tables(C.byref(self.dims), self.words.ctypes.data_as(C.c_void_p), n), "dns_frame_prep_tables")
+        self.H, self.W = self.stage_hw[0] - 2 * self.edge, self.stage_hw[1] - 2 * self.edge
+        self.dev = torch.from_numpy(self.words).to(torch.device(device))
+        self.device = self.dev.device
+        self._parts = {}
+
+    @staticmethod
+    def _pair(v, what):
+        try:
+            h, w = (int(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError(f"frame_prep_tables: {what} must be (H, W), got {v!r}") from None
+        if h < 1 or w < 1:
+            raise ValueError(f"frame_prep_tables: {what} {v!r}")
+        return h, w
+
+    def parts(self, device=None):
+        """The tables by name, as views of the blob on ``device`` (default: the tables' own): ``cv_x`` / ``cv_y`` / ``tb_x`` /
+        ``tb_y`` = (index int64, weights fp32 [.,2]) of the cv2 and torch linear stages, ``tn_x`` / ``tn_y`` / ``cn_x`` / ``cn_y`` =
+        the index of the torch and cv2 nearest stages (csrc/frame_prep_plan.hpp states the layout)."""
+        device = self.device if device is None else torch.device(device)
+        if device in self._parts:
+            return self._parts[device]
+        blob = self.dev if device == self.device else torch.from_numpy(self.words).to(device)
+        (_, _), (Hd, Wd), (Hs, Ws) = self.color_hw, self.depth_hw, self.stage_hw
+        out, o = {}, 0
+        for name, n in (("cv_x", Wd), ("cv_y", Hd), ("tb_x", Ws), ("tb_y", Hs)):
+            out[name] = (blob[o:o + n].long(), blob[o + n:o + 3 * n].view(torch.float32).reshape(n, 2))
+            o += 3 * n
+        for name, n in (("tn_x", Ws), ("tn_y", Hs), ("cn_x", Wd), ("cn_y", Hd)):
+            out[name] = blob[o:o + n].long()
+            o += n
+        assert o == blob.numel()
+        self._parts[device] = out
+        return out
+
+
+def frame_prep_tables(color_hw, depth_hw, label_hw=None, crop_size=None, crop_edge=0, device="cuda") -> FramePrepTables:
+    """Tables for colour images of ``color_hw``, depth images of ``depth_hw``, label images of ``label_hw`` (None: no labels),
+    ``cfg['cam']['crop_size']`` (None: not set) and ``cfg['cam']['crop_edge']``."""
+    return FramePrepTables(color_hw, depth_hw, label_hw, crop_size, crop_edge, device)
+
+
+def _frame_prep_args(color, depth, label, lut, tables, method):
+    """Argument checks of prepare_frames, ahead of any launch -> (color, depth, label, n, single, method)."""
+    if not isinstance(tables, FramePrepTables):
+        raise ValueError("prepare_frames: tables must come from ops.frame_prep_tables")
+    if not isinstance(color, torch.Tensor) or not isinstance(depth, torch.Tensor):
+        raise ValueError("prepare_frames: color and depth must be tensors")
+    if method is None:
+        method = PREPARE_FRAMES_DEFAULT if color.is_cuda else "torch"
+    if method not in PREPARE_FRAMES_METHODS:
+        raise ValueError(f"prepare_frames: method {method!r} (one of {PREPARE_FRAMES_METHODS})")
+    if color.dtype != torch.uint8 or color.dim() not in (3, 4) or color.shape[-1] != 3:
+        raise ValueError(f"prepare_frames: color must be uint8 [n,Hc,Wc,3] or [Hc,Wc,3], got {color.dtype} {tuple(color.shape)}")
+    single = color.dim() == 3
+    if depth.dtype != torch.uint16 or depth.dim() != color.dim() - 1:
+        raise ValueError(f"prepare_frames: depth must be uint16 [n,Hd,Wd] ([Hd,Wd] for one frame), got {depth.dtype} {tuple(depth.shape)}")
+    if label is not None:
+        if not isinstance(label, torch.Tensor) or label.dtype not in (torch.uint8, torch.uint16) or label.dim() != depth.dim():
+            raise ValueError("prepare_frames: label must be a uint8 or uint16 tensor [n,Hl,Wl] ([Hl,Wl] for one frame) or None")
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.int32 or tuple(lut.shape) != (LABEL_VALUES,):
+            raise ValueError(f"prepare_frames: lut must be an int32 [{LABEL_VALUES}] tensor")
+    if single:
+        color, depth, label = color[None], depth[None], None if label is None else label[None]
+    n = int(color.shape[0])
+    if tuple(color.shape[1:3]) != tables.color_hw or tuple(depth.shape) != (n,) + tables.depth_hw:
+        raise ValueError(f"prepare_frames: colour {tuple(color.shape)} / depth {tuple(depth.shape)} for tables of colour "
+                         f"{tables.color_hw} and depth {tables.depth_hw}, n = {n}")
+    if (label is None) != (tables.label_hw is None) or (label is not None and tuple(label.shape) != (n,) + tables.label_hw):
+        raise ValueError(f"prepare_frames: label {None if label is None else tuple(label.shape)} for tables of labels {tables.label_hw}, n = {n}")
+    if n > 65535:
+        raise ValueError(f"prepare_frames: {n} frames (must be <= 65535)")
+    ts = [color, depth] + ([label, lut] if label is not None else [])
+    if any(t.device != color.device for t in ts):
+        raise ValueError("prepare_frames: color, depth, label and lut must live on one device")
+    if any(not t.is_contiguous() for t in ts):
+        raise ValueError("prepare_frames: color, depth, label and lut must be contiguous")
+    if method == "kernel":
+        require_cuda(*ts)
+        if tables.dev.device != color.device:
+            raise ValueError(f"prepare_frames: the tables live on {tables.dev.device}, the images on {color.device}")
+    return color, depth, label, n, single, method
+
+
+def _prepare_frames_torch(color, depth, label, lut, tables, png_depth_scale, scale, bgr):
+    """The stages of include/dns_hip.h composed of torch ops on whole images (fp32 products and sums; their fusion is the library's)."""
+    t = tables.parts(color.device)
+    e, (Hs, Ws) = tables.edge, tables.stage_hw
+    # the two fp32 divisions, correctly rounded: torch turns a division by a Python scalar into a product with its reciprocal on the
+    # device, and the device's fp32 quotient need not be the IEEE one.  A float64 quotient of two fp32 numbers rounded to fp32 is (53
+    # >= 2 24 + 2 bits: the second rounding cannot change the result), and a tensor divisor keeps the division a division.
+    div = lambda x, by: (x.to(torch.float64) / torch.full((1,), float(np.float32(by)), dtype=torch.float64, device=x.device)).to(torch.float32)
+    c = div(color, 255.0)
+    if bgr:
+        c = c.flip(-1)
+
+    def linear(img, ix, wx, iy, wy, src_h, src_w):
+        x1, y1 = (ix + 1).clamp(max=src_w - 1), (iy + 1).clamp(max=src_h - 1)
+        h = img[:, :, ix] * wx[:, 0, None] + img[:, :, x1] * wx[:, 1, None]
+        return h[:, iy] * wy[:, 0, None, None] + h[:, y1] * wy[:, 1, None, None]
+
+    if tables.color_hw != tables.depth_hw:
+        c = linear(c, *t["cv_x"], *t["cv_y"], *tables.color_hw)
+    if tables.stage_hw != tables.depth_hw:
+        c = linear(c, *t["tb_x"], *t["tb_y"], *tables.depth_hw)
+    d = div(depth, png_depth_scale) * float(np.float32(scale))
+    d = d[:, t["tn_y"]][:, :, t["tn_x"]]
+    crop = lambda img: img[:, e:Hs - e, e:Ws - e].contiguous()
+    lab = None
+    if label is not None:
+        lab = label.to(torch.int64)[:, t["cn_y"]][:, :, t["cn_x"]]
+        lab = lut.to(torch.int64)[lab][:, t["tn_y"]][:, :, t["tn_x"]]
+        lab = crop(lab)
+    return crop(c), crop(d), lab
+
+
+def prepare_frames(color: torch.Tensor, depth: torch.Tensor, label: Optional[torch.Tensor], lut: Optional[torch.Tensor],
+                   tables: FramePrepTables, png_depth_scale: float, scale: float = 1.0, bgr: bool = False, method: Optional[str] = None):
+    """``BaseDataset.__getitem__`` (datas/slam_datasets.py:85-149) on the raw images of n frames: color uint8 [n,Hc,Wc,3] (``bgr``:
+    channel order B, G, R, as cv2.imread returns), depth uint16 [n,Hd,Wd], label uint8 / uint16 [n,Hl,Wl] or None, lut int32 [65536]
+    (the class of every raw label value; None without labels) -> (color fp32 [n,H,W,3] in RGB, depth fp32 [n,H,W], label int64
+    [n,H,W] or None).  Inputs without the frame dimension give outputs without it.  The stages, their order and their rounding are
+    the ones include/dns_hip.h states.
+
+    ``method="kernel"``: one launch (csrc/frame_prep.hip); a frame's bits depend on nothing but the frame.  ``method="torch"``: the
+    same definition composed of torch ops over whole images, which also runs on CPU tensors; depth and label are the kernel's, its
+    colour may differ in the last bits where the library fuses a product with a sum.  None: ``PREPARE_FRAMES_DEFAULT`` for device
+    tensors, "torch" for CPU tensors.  Wrong dtypes, shapes that do not match the tables, non-contiguous tensors, mixed devices
+    and, for "kernel", CPU tensors raise ValueError before anything is launched."""
+    color, depth, label, n, single, method = _frame_prep_args(color, depth, label, lut, tables, method)
+    pds, sc = float(png_depth_scale), float(scale)
+    if not (math.isfinite(pds) and pds != 0.0 and float(np.float32(pds)) != 0.0 and math.isfinite(sc)):
+        raise ValueError(f"prepare_frames: png_depth_scale {png_depth_scale}, scale {scale}")
+    if method == "torch":
+        oc, od, ol = _prepare_frames_torch(color, depth, label, lut, tables, pds, sc, bool(bgr))
+    else:
+        dev = color.device
+        oc = torch.empty(n, tables.H, tables.W, 3, dtype=torch.float32, device=dev)
+        od = torch.empty(n, tables.H, tables.W, dtype=torch.float32, device=dev)
+        ol = None if label is None else torch.empty(n, tables.H, tables.W, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.dns_prepare_frames(ptr(color), int(bool(bgr)), ptr(depth), ptr(label), 0 if label is None else label.element_size(),
+                                         ptr(lut) if label is not None else None, C.byref(tables.dims), ptr(tables.dev),
+                                         tables.dev.numel(), n, pds, sc, ptr(oc), ptr(od), ptr(ol), stream_ptr()), "dns_prepare_frames")
+    if single:
+        oc, od, ol = oc[0], od[0], None if ol is None else ol[0]
+    return oc, od, ol
+
+
+def label_first_seen(labels: torch.Tensor, method: Optional[str] = None) -> torch.Tensor:
+    """labels uint8 / uint16 of any shape (frames concatenated, row-major) -> int32 [65536]: for every value the smallest flat index
+    at which it occurs, -1 for a value that does not occur.  ``cal_class_n``'s ``set(label_data.flatten())`` iterates in an order
+    that depends on the first occurrences of the distinct values alone, so this is all of a label image the class numbering needs.
+    ``method="kernel"``: an integer atomic minimum on the device (the same for every call); ``"torch"``: a scatter-reduce, also on
+    CPU tensors; None: "kernel" for device tensors, "torch" for CPU tensors."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("label_first_seen: labels must be a uint8 or uint16 tensor")
+    if method is None:
+        method = "kernel" if labels.is_cuda else "torch"
+    if method not in PREPARE_FRAMES_METHODS:
+        raise ValueError(f"label_first_seen: method {method!r} (one of {PREPARE_FRAMES_METHODS})")
+    if not labels.is_contiguous():
+        raise ValueError("label_first_seen: labels must be contiguous")
+    n = labels.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"label_first_seen: {n} pixels (must be < 2^31)")
+    if method == "torch":
+        big = torch.full((LABEL_VALUES,), 1 << 31, dtype=torch.int64, device=labels.device)
+        big.scatter_reduce_(0, labels.reshape(-1).to(torch.int64), torch.arange(n, device=labels.device), "amin")
+        return torch.where(big == 1 << 31, torch.full_like(big, -1), big).to(torch.int32)
+    require_cuda(labels)
+    first = torch.empty(LABEL_VALUES, dtype=torch.int32, device=labels.device)
+    with torch.cuda.device(labels.device):
+        check(lib.dns_label_first_seen(ptr(labels), labels.element_size(), n, ptr(first), stream_ptr()), "dns_label_first_seen")
+    return first

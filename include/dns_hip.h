@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 27
+#define DNS_ABI_VERSION 28
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -1080,6 +1080,48 @@ int dns_lpips_head(const float* fa, const float* fb, const float* lin, uint32_t 
                    void* stream);
 int dns_lpips_finish(const double* const* partials, const uint32_t* h, const uint32_t* w, uint32_t n_layers, uint32_t F, double* lpips,
                      double* layers, void* stream);
+
+/* ---- frame preparation (BaseDataset.__getitem__, datas/slam_datasets.py:85-149; csrc/frame_prep.hip, csrc/frame_prep_plan.hpp;
+ * ABI v28) -------------------------------------------------------------------------------------------------------------------------
+ * The raw 8/16-bit images of n frames -> the float colour, float depth and int64 class image the reference hands the tracker and
+ * the mapper, in ONE launch, every output pixel on its own through the reference's stages in the reference's order:
+ *   colour  1. fl32(u8) / 255.0f, a correctly rounded fp32 division, per tap;
+ *           2. cv2.resize(color, (Wd, Hd)), bilinear on float32: the horizontal pass a w0 + b w1 first, the vertical pass on its
+ *              results, each product and each sum rounded to fp32;
+ *           3. F.interpolate(mode='bilinear', align_corners=True) to (Hs, Ws): horizontal, then vertical, rounded alike;
+ *           4. the crop [edge, Hs - edge) x [edge, Ws - edge).
+ *   depth   fl32(fl32(u16) / fl32(png_depth_scale)) * fl32(scale); F.interpolate(mode='nearest') to (Hs, Ws); the crop.
+ *   label   cv2.resize(..., INTER_NEAREST) to (Wd, Hd); lut[value]; F.interpolate(mode='nearest'); the crop.
+ * A stage whose source and destination sizes are equal is the identity (so without crop_size: Hs, Ws = Hd, Wd), and the colour of
+ * all-identity dims is fl32(u8) / 255 bit for bit.  The resampling rules are the tables' (frame_prep_plan.hpp states each); the two
+ * cv2 stages follow OpenCV's published rule, not arrays OpenCV wrote.  cv2.undistort is not built.
+ *
+ * dns_frame_prep_table_words: words of the table blob of dims d [host]; 0 = refused (a side of 0 or above 32768, labels with one
+ *   side 0, 2 edge >= Hs or Ws).  Hl = Wl = 0: no label image.
+ * dns_frame_prep_tables: fills words [host, n_words = dns_frame_prep_table_words(d)] on the host; the caller copies it to the device.
+ * dns_prepare_frames: color uint8 [n,Hc,Wc,3] (bgr != 0: channel order B, G, R), depth uint16 [n,Hd,Wd], label uint8
+ *   (label_bytes 1) or uint16 (2) [n,Hl,Wl] or NULL with label_bytes 0 and Hl = Wl = 0, lut int32 [65536] (NULL without labels),
+ *   tables: the DEVICE copy of the blob of d, table_words its size (checked against d) -> out_color fp32 [n,H,W,3] in RGB,
+ *   out_depth fp32 [n,H,W], out_label int64 [n,H,W] (NULL without labels), H = Hs - 2 edge, W = Ws - 2 edge.  n <= 65535.  No
+ *   atomics; every table index is clamped into its image before it is used, so no read leaves the images whatever the blob
+ *   holds; a frame's bits do not depend on n.
+ * dns_label_first_seen: label uint8 / uint16 [n_pixels] (frames concatenated; n_pixels < 2^31) -> first int32 [65536]: for every
+ *   value the smallest flat index at which it occurs, -1 for a value that does not.  Integer atomic minimum: the same for every call.
+ *   (This is what cal_class_n's set(label_data.flatten()) needs: a set's iteration order depends on the order in which DISTINCT
+ *   keys arrive, i.e. on first occurrences.) */
+typedef struct DnsFramePrepDims {
+  uint32_t Hc, Wc;   /* colour image */
+  uint32_t Hd, Wd;   /* depth image: the size cv2.resize takes colour and labels to */
+  uint32_t Hl, Wl;   /* label image; 0, 0 = none */
+  uint32_t Hs, Ws;   /* cfg['cam']['crop_size']; Hd, Wd where the config sets none */
+  uint32_t edge;     /* cfg['cam']['crop_edge'] */
+} DnsFramePrepDims;
+uint64_t dns_frame_prep_table_words(const DnsFramePrepDims* d);
+int dns_frame_prep_tables(const DnsFramePrepDims* d, int32_t* words, uint64_t n_words);
+int dns_prepare_frames(const uint8_t* color, int bgr, const uint16_t* depth, const void* label, int label_bytes, const int32_t* lut,
+                       const DnsFramePrepDims* d, const int32_t* tables, uint64_t table_words, uint32_t n, float png_depth_scale,
+                       float scale, float* out_color, float* out_depth, int64_t* out_label, void* stream);
+int dns_label_first_seen(const void* label, int label_bytes, uint64_t n_pixels, int32_t* first, void* stream);
 
 #ifdef __cplusplus
 }
