@@ -9,6 +9,7 @@ Mirrors of the reference interface (same names / argument meaning):
   decoder.Decoder                <- reference models/decoder.py:7-27
   common.*                       <- reference utils/common.py (live render math)
   mapping.Mapper / tracking.Tracker optimise-step bodies <- reference slams/mapping.py, slams/tracking.py
+  slam.DNS_SLAM                  <- reference slams/dns_slam.py with the frame loops of Mapper.run / Tracker.run ('strict')
 """
 from . import _lib  # noqa: F401  (loads libdns_hip.so or raises)
 

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DNS_HIP_LIB") or os.path.join(_HERE, "libdns_hip.so")   # override: A/B of two builds
 DNS_MAX_LEVELS = 32
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class DnsGridMeta(C.Structure):
@@ -190,6 +190,8 @@ SIGNATURES = {
     "dns_prepare_frames": (C.c_int, [_P, _I, _P, _P, _I, _P, C.POINTER(DnsFramePrepDims), _P, C.c_uint64, _U, C.c_float, C.c_float,
                                      _P, _P, _P, _P]),
     "dns_label_first_seen": (C.c_int, [_P, _I, C.c_uint64, _P, _P]),
+    "dns_keyframe_overlap": (C.c_int, [_P, _U, _P, _U, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _I, C.c_double, _P, _P]),
+    "dns_vis_panels": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _U, _U, _U, C.c_float, _U, _U, _P, _P, _P]),
 }
 
 

@@ -10,8 +10,9 @@ the hot path:
     compute_*_loss               :110-126
     set_optimizer / optimize     :438-468, :839-949 (iteration driver)
 
-Keyframe selection, visualisation, meshing, checkpointing and the process loop (``run``) are out of scope
-(components 8-14).
+    frame_vis                    :638-724 (the sheet composed on the device, ops.vis_panels)
+
+The frame loop (``run`` :952-1146) is ``dns_slam_amd.slam.DNS_SLAM``; meshing and checkpointing are ``meshing`` / ``checkpoint``.
 """
 from __future__ import annotations
 
@@ -121,6 +122,7 @@ class Mapper:
         self.is_BA = True
         self.keyframe_dict, self.keyframe_list = [], []  # filled by the caller's frame loop (reference Mapper.run :975,1085)
         self.keyframe_selector = None                    # optional host-side keyframe choice (set_target_refer_frames)
+        self.overlap_scorer = None                       # optional (pts, keyframe_dict) -> percent: keyframe_selection_overlap's projection
         self.mapping_mode = "global"                     # 'global' | 'overlap' (slams/mapping.py:350-356; run() alternates them)
         self.encoder = None                              # frozen image stem (dns_slam_amd.encoder.ResNet) or None
         self.dist = None                                 # dns_slam_amd.dist.DistCtx for ray-batch data parallelism
@@ -833,6 +835,45 @@ class Mapper:
         c2w = [kfs[r]["est_c2w"].to(dev).float() for r in pair] + [cur_c2w.to(dev).float()]
         return {"gt_color": torch.stack(color, 0), "est_c2w": torch.stack(c2w, 0), "kf_idx": pair + [-1]}
 
+    def _class2label_lut(self):
+        """``class2label_dict`` (class index -> dataset label, what frame_vis' map_function looks up, :701-702) as an int32 device
+        table; a class without an entry maps to itself, as ``dict.get(value, value)``.  None without a dictionary."""
+        d = self.class2label_dict
+        if not d:
+            return None
+        cached = getattr(self, "_vis_lut", None)
+        if cached is None or cached[0] is not d or cached[1] != len(d):
+            items = [(int(k), int(v)) for k, v in d.items() if int(k) >= 0]
+            lut = torch.arange(max(k for k, _ in items) + 1 if items else 1, dtype=torch.int32)
+            for k, v in items:
+                lut[k] = v
+            self._vis_lut = cached = (d, len(d), lut.to(self.device))
+        return cached[2]
+
+    @torch.no_grad()
+    def frame_vis(self, idx, color, depth, label, gt_c2w, cur_c2w, out_dir=None):
+        """The reference's ``frame_vis`` (slams/mapping.py:638-724) without its host work: the frame is re-rendered at ``cur_c2w``
+        (``render_frame``; with ``self.encoder`` set the reference views are the current frame's bundle -- the two latest keyframes
+        and the frame itself, :644-681 -- through ``vis_refer_frames``, which draws no random numbers where the reference's
+        set_target_refer_frames call does), and fig_plot's 3 x 3 sheet is composed on the device by ``ops.vis_panels`` (labels
+        through ``class2label_dict``, :701-718).  The sheet (uint8 [3H + 16, 3W + 16, 3], device) is returned; with ``out_dir`` it is
+        also written to ``{out_dir}/{idx:05d}.png`` -- the ONE host read of the call (the reference: six full images).  PNG in place
+        of the reference's JPEG figure; no titles or axes.  ``gt_c2w`` is part of the reference's signature and unused there too.
+        ``is_BA`` is left as it is (the reference clears it, :640, and every optimize() sets it again before reading it)."""
+        dev = self.device
+        color, depth, label = color.to(dev).float().contiguous(), depth.to(dev).float().contiguous(), label.to(dev).contiguous()
+        cur_c2w = torch.as_tensor(cur_c2w).detach().float().cpu()          # render_frame takes its quaternion on the host anyway
+        refer = self.vis_refer_frames(color, cur_c2w) if getattr(self, "encoder", None) is not None else None
+        pred_color, pred_depth, pred_label = self.render_frame(color, depth, label, cur_c2w, refer_frames=refer)
+        sheet, _ = ops.vis_panels(color, pred_color.float().contiguous(), depth, pred_depth.float().contiguous(), label,
+                                  pred_label.contiguous(), label_lut=self._class2label_lut())
+        if out_dir is not None:
+            import os
+            from .visualize import write_png
+            os.makedirs(out_dir, exist_ok=True)
+            write_png(os.path.join(out_dir, f"{idx:05d}.png"), sheet.cpu().numpy())
+        return sheet
+
     # ------------------------------------------------------------------ slams/mapping.py:887-907
     def iteration_loss(self, samples, lambda_lt=10.0, smooth=True, u_offset=None, u_jitter=None, strict=False):
         # The smoothness branch (lattice encode + coarse network, forward and -- since autograd replays a node on its
@@ -958,14 +999,20 @@ class Mapper:
         pts = (rays_o[:, None, :] + rays_d[:, None, :] * z_vals[..., None]).reshape(-1, 3)              # [pixels * N_samples, 3]
         if len(keyframe_dict) == 0:
             return []
-        w2c = torch.linalg.inv(torch.stack([torch.as_tensor(kf["est_c2w"]).to(dev).float() for kf in keyframe_dict]))
-        cam = torch.einsum("kij,nj->kni", w2c[:, :3, :3], pts) + w2c[:, None, :3, 3]                     # [n_kf, n, 3]
-        x, y, zc = -cam[..., 0], cam[..., 1], cam[..., 2]
-        z = zc + 1e-5
-        u, v = (fx * x + cx * zc) / z, (fy * y + cy * zc) / z
-        edge = 10
-        inside = (u < W - edge) & (u > edge) & (v < H - edge) & (v > edge) & (z < 0)
-        percent = inside.float().mean(dim=1).cpu().numpy()
+        if getattr(self, "overlap_scorer", None) is not None:
+            # the projection block alone is replaced (keyframes.KeyframeBank.overlap_scorer: ops.keyframe_overlap on the bank's pose
+            # table, count / P in float64 as the reference's mask.sum() / uv.shape[0]); the draw above and the sort, threshold and
+            # permutation below stay, so a seeded run consumes both generators as before
+            percent = np.asarray(self.overlap_scorer(pts, keyframe_dict), dtype=np.float64)
+        else:
+            w2c = torch.linalg.inv(torch.stack([torch.as_tensor(kf["est_c2w"]).to(dev).float() for kf in keyframe_dict]))
+            cam = torch.einsum("kij,nj->kni", w2c[:, :3, :3], pts) + w2c[:, None, :3, 3]                 # [n_kf, n, 3]
+            x, y, zc = -cam[..., 0], cam[..., 1], cam[..., 2]
+            z = zc + 1e-5
+            u, v = (fx * x + cx * zc) / z, (fy * y + cy * zc) / z
+            edge = 10
+            inside = (u < W - edge) & (u > edge) & (v < H - edge) & (v > edge) & (z < 0)
+            percent = inside.float().mean(dim=1).cpu().numpy()
         self.last_overlap_percent = percent                      # inspection / tests
         order = sorted(range(len(keyframe_dict)), key=lambda i: percent[i], reverse=True)
         selected = [i for i in order if percent[i] > th]

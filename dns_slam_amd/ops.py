@@ -2635,3 +2635,72 @@ def label_first_seen(labels: torch.Tensor, method: Optional[str] = None) -> torc
     with torch.cuda.device(labels.device):
         check(lib.dns_label_first_seen(ptr(labels), labels.element_size(), n, ptr(first), stream_ptr()), "dns_label_first_seen")
     return first
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# keyframe overlap and frame_vis's sheet (csrc/keyframes.hip, csrc/vis_panels.hip; include/dns_hip.h, ABI v29)
+def keyframe_overlap(points: torch.Tensor, c2w: torch.Tensor, H: int, W: int, fx: float, fy: float, cx: float, cy: float,
+                     edge: int = 10, eps: float = 1e-5) -> torch.Tensor:
+    """The projection block of ``keyframe_selection_overlap`` (slams/mapping.py:208-226) for all keyframes in one launch and without
+    a host read: points fp32 [P,3], c2w fp32 [n,4,4] (camera-to-world) -> int32 [n], per keyframe the number of points that project
+    more than ``edge`` pixels inside the H x W image with z < 0.  The arithmetic is float64, one rounding per operation, in the order
+    include/dns_hip.h states; tests/keyframe_overlap_ref.py restates it in numpy and the counts are equal to it.  A point or pose
+    with a non-finite entry, and a singular pose, count nothing.  ``P == 0`` gives zeros and ``n == 0`` an empty tensor, without a
+    launch."""
+    require_cuda(points, c2w)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"keyframe_overlap: points must be fp32 [P,3], got {points.dtype} {tuple(points.shape)}")
+    if c2w.dtype != torch.float32 or c2w.dim() != 3 or tuple(c2w.shape[1:]) != (4, 4):
+        raise ValueError(f"keyframe_overlap: c2w must be fp32 [n,4,4], got {c2w.dtype} {tuple(c2w.shape)}")
+    if points.device != c2w.device:
+        raise ValueError("keyframe_overlap: points and c2w are on different devices")
+    P, n = points.shape[0], c2w.shape[0]
+    if P == 0 or n == 0:
+        return torch.zeros(n, dtype=torch.int32, device=points.device)
+    out = torch.empty(n, dtype=torch.int32, device=points.device)
+    with torch.cuda.device(points.device):
+        check(lib.dns_keyframe_overlap(ptr(points), P, ptr(c2w), n, int(H), int(W), float(fx), float(fy), float(cx), float(cy),
+                                       int(edge), float(eps), ptr(out), stream_ptr()), "dns_keyframe_overlap")
+    return out
+
+
+def vis_panels(gt_color: torch.Tensor, est_color: torch.Tensor, gt_depth: torch.Tensor, est_depth: torch.Tensor,
+               gt_label: torch.Tensor, est_label: torch.Tensor, label_lut: Optional[torch.Tensor] = None, max_label: float = 101,
+               gap: int = 8, background: int = 255):
+    """``fig_plot``'s 3 x 3 sheet (utils/common.py:682-745) on the device: rows depth, colour, label; columns input, generated,
+    |difference|; panels at native resolution, ``gap`` pixels of ``background`` between them -> (uint8 [3H + 2 gap, 3W + 2 gap, 3],
+    vmax), vmax a 0-dim fp32 device tensor: the largest finite positive ``gt_depth`` (0 without one), which scales the depth row.
+    Colours fp32 [H,W,3], depths fp32 [H,W]; labels [H,W] of any integer or float dtype (taken as int32), mapped through
+    ``label_lut`` (int32 [n]: the class -> label table; entries outside it stay as they are) and scaled by ``max_label``.  The byte
+    rules are include/dns_hip.h's: scalar panels are matplotlib's ``plasma(Normalize(0, vmax)(x), bytes=True)``, a non-finite scalar
+    pixel takes the background colour (matplotlib leaves it transparent).  Titles, axes and the JPEG are not rebuilt.  No host read."""
+    require_cuda(gt_color, est_color, gt_depth, est_depth, gt_label, est_label, label_lut)
+    if gt_depth.dim() != 2:
+        raise ValueError(f"vis_panels: gt_depth must be [H,W], got {tuple(gt_depth.shape)}")
+    H, W = gt_depth.shape
+    if H < 1 or W < 1:
+        raise ValueError("vis_panels: an empty image")
+    for name, t, shape in (("gt_color", gt_color, (H, W, 3)), ("est_color", est_color, (H, W, 3)), ("gt_depth", gt_depth, (H, W)),
+                           ("est_depth", est_depth, (H, W))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"vis_panels: {name} must be fp32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    labels = []
+    for name, t in (("gt_label", gt_label), ("est_label", est_label)):
+        if tuple(t.shape) != (H, W):
+            raise ValueError(f"vis_panels: {name} must be [{H},{W}], got {tuple(t.shape)}")
+        labels.append(t if t.dtype == torch.int32 else t.to(torch.int32))
+    if label_lut is not None and (label_lut.dtype != torch.int32 or label_lut.dim() != 1 or label_lut.numel() == 0):
+        raise ValueError("vis_panels: label_lut must be a non-empty int32 vector")
+    dev = gt_depth.device
+    if any(t is not None and t.device != dev for t in (gt_color, est_color, est_depth, gt_label, est_label, label_lut)):
+        raise ValueError("vis_panels: tensors on different devices")
+    gap, background = int(gap), int(background)
+    if not (0 <= gap <= 4096 and 0 <= background <= 255):
+        raise ValueError(f"vis_panels: gap {gap} (0..4096), background {background} (0..255)")
+    out = torch.empty(3 * H + 2 * gap, 3 * W + 2 * gap, 3, dtype=torch.uint8, device=dev)
+    vmax = torch.empty((), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dns_vis_panels(ptr(gt_color), ptr(est_color), ptr(gt_depth), ptr(est_depth), ptr(labels[0]), ptr(labels[1]),
+                                 ptr(label_lut), 0 if label_lut is None else label_lut.numel(), H, W, float(max_label), gap, background,
+                                 ptr(out), ptr(vmax), stream_ptr()), "dns_vis_panels")
+    return out, vmax

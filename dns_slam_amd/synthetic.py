@@ -113,3 +113,32 @@ def make_scene(n_frames=4, cam=None, bound=None, seed=0):
 
 def clone_cfg(cfg):
     return copy.deepcopy(cfg)
+
+
+class SyntheticSequence:
+    """A sequence of the box room as the dataset interface ``slam.DNS_SLAM`` takes (``__len__``, ``__getitem__ -> (idx, color,
+    depth, label, c2w)``, ``n_class``, ``class2label_dict``): n frames on a short arc of ``make_pose``'s circle, ``step`` radians
+    apart so that consecutive views overlap, rendered exactly by ``render_frame``.  Frames are CPU tensors; labels are float class
+    indices 0..7, as ``make_scene`` makes them."""
+
+    def __init__(self, n=8, H=48, W=64, fx=50.0, step=0.04, seed=0, bound=None):
+        self.cam = camera(H=H, W=W, fx=fx, fy=fx)
+        self.bound = load_bound(bound or ROOM0_BOUND)
+        room = self.bound.clone()
+        room[:, 0] += 0.6
+        room[:, 1] -= 0.6
+        centre = tuple(float(v) for v in (self.bound[:, 0] + self.bound[:, 1]) / 2)
+        self.frames = []
+        for f in range(n):
+            c2w = make_pose(0.3 + step * f, center=centre, radius=0.5 + 0.01 * math.sin(f))
+            color, depth, label = render_frame(c2w, self.cam, room, seed * 100 + f)
+            self.frames.append((color, depth, label, c2w))
+        self.n_class = 8
+        self.class2label_dict = {c: 10 * c + 1 for c in range(8)}
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __getitem__(self, i):
+        color, depth, label, c2w = self.frames[i]
+        return i, color, depth, label, c2w

@@ -6,7 +6,7 @@
     renderer              :188-214  (coarse-only)
     track_frame           the per-frame loop body :313-340 (keep-best-pose included)
 
-The process loop (``run`` :229: data loading, mapper synchronisation, logging) is out of scope.
+The frame loop (``run`` :229: data loading, mapper synchronisation, logging) is ``dns_slam_amd.slam.DNS_SLAM``.
 """
 from __future__ import annotations
 

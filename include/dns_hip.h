@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DNS_ABI_VERSION 28
+#define DNS_ABI_VERSION 29
 #define DNS_MAX_LEVELS 32
 
 #define DNS_OK 0
@@ -1122,6 +1122,41 @@ int dns_prepare_frames(const uint8_t* color, int bgr, const uint16_t* depth, con
                        const DnsFramePrepDims* d, const int32_t* tables, uint64_t table_words, uint32_t n, float png_depth_scale,
                        float scale, float* out_color, float* out_depth, int64_t* out_label, void* stream);
 int dns_label_first_seen(const void* label, int label_bytes, uint64_t n_pixels, int32_t* first, void* stream);
+
+/* ---- keyframe overlap (the projection block of keyframe_selection_overlap, slams/mapping.py:208-226; csrc/keyframes.hip;
+ * ABI v29) -----------------------------------------------------------------------------------------------------------------------
+ * dns_keyframe_overlap: pts fp32 [P,3], c2w fp32 [n,4,4] (row-major, all on the device) -> out int32 [n]: per keyframe the number
+ * of points that project more than `edge` pixels inside the H x W image with z < 0.  No host read.  The arithmetic, every
+ * operation rounded once (no contraction), tests/keyframe_overlap_ref.py being the numpy restatement that the counts must EQUAL:
+ *   1. the pose and the point are widened to float64;
+ *   2. w = inverse(c2w) by the adjugate: the six 2 x 2 minors s0..s5 of rows 0-1 and c0..c5 of rows 2-3 (column pairs 01, 02, 03, 12,
+ *      13, 23), det = ((((s0 c5 - s1 c4) + s2 c3) + s3 c2) - s4 c1) + s5 c0, and every entry of rows 0-2 as its three-term
+ *      cofactor sum, in the order csrc/keyframes.hip writes out, divided by det;
+ *   3. camera coordinates ((w_r0 x + w_r1 y) + w_r2 z) + w_r3 for r = 0, 1, 2; xc is negated;
+ *   4. ze = zc + eps; u = (fx xc + cx zc) / ze, v = (fy yc + cy zc) / ze;
+ *   5. u, v rounded to fp32; inside = u < fl32(W - edge), u > fl32(edge), v < fl32(H - edge), v > fl32(edge), ze < 0, all strict.
+ * A point with a non-finite coordinate is outside; a pose with a non-finite entry, or whose determinant is 0 or non-finite, counts 0.
+ * Counting is a wave ballot per pass and one integer atomic add per workgroup into out (zeroed first by a kernel): order-free.
+ * n == 0: nothing is done; P == 0: out is zeroed.  n <= 65535, P < 2^31, H, W, edge <= 2^24. */
+int dns_keyframe_overlap(const float* pts, uint32_t P, const float* c2w, uint32_t n, int H, int W, double fx, double fy, double cx,
+                         double cy, int edge, double eps, int32_t* out, void* stream);
+
+/* ---- visualisation panels (fig_plot, utils/common.py:682-745, as frame_vis calls it, slams/mapping.py:638-724; csrc/vis_panels.hip,
+ * csrc/plasma_lut.hpp; ABI v29) ---------------------------------------------------------------------------------------------------
+ * dns_vis_panels: gt_color, est_color fp32 [H,W,3], gt_depth, est_depth fp32 [H,W], gt_label, est_label int32 [H,W], label_lut
+ * int32 [n_lut] or NULL -> out uint8 [3H + 2 gap, 3W + 2 gap, 3] and vmax_bits (one word: the bits of the depth row's vmax).
+ * Panel (r, c) starts at pixel (r (H + gap), c (W + gap)); rows: depth, colour, label; columns: input, generated, |input -
+ * generated| (fp32 for depth and colour; on the mapped integer labels for the label row).  Everything outside a panel = background.
+ *   scalar panels: index = trunc(fl32(fl32(x / vmax) * 256)), below 0 -> 0, 256 and above -> 255, then plasma_lut.hpp's triple: what
+ *     matplotlib's plasma(Normalize(0, vmax)(x), bytes=True) gives.  vmax == 0 -> index 0.  Depth: vmax = the largest finite
+ *     positive gt depth (0 if there is none), an integer atomic maximum on the floats' bits: the same on every call.  Labels:
+ *     vmax = max_label, after label = label_lut[label] where 0 <= label < n_lut (else unchanged, as dict.get(value, value)).
+ *     A non-finite scalar pixel takes the background colour (matplotlib draws its "bad" colour, transparent, there).
+ *   colour panels: trunc(fl32(clip(x, 0, 1) * 255)) per channel; a NaN is taken as 0.
+ * Titles, axes and the JPEG encoding of the reference's figure are not rebuilt.  H, W <= 16384, gap <= 4096, background <= 255. */
+int dns_vis_panels(const float* gt_color, const float* est_color, const float* gt_depth, const float* est_depth,
+                   const int32_t* gt_label, const int32_t* est_label, const int32_t* label_lut, uint32_t n_lut, uint32_t H, uint32_t W,
+                   float max_label, uint32_t gap, uint32_t background, uint8_t* out, uint32_t* vmax_bits, void* stream);
 
 #ifdef __cplusplus
 }
