@@ -3,9 +3,11 @@
 // out at the top of mesh_raster.hip and in include/dns_hip.h; tests/raster_ref.py restates it.  Both units are compiled with
 // -ffp-contract=off (Makefile): every operation below is one fp32 rounding in the order written, so the two kernels compute
 // the same bits for the same (triangle, view, pixel) -- the depth image of dns_render_mesh is dns_rasterize_depth's.
+// At the end, the host side the two launch wrappers share: the workspace parts they have in common and the cut into launches.
 #pragma once
 #include <algorithm>
 #include "common.hpp"
+#include "ws_carve.hpp"
 namespace dns {
 
 constexpr int RS_BLOCK = 256;
@@ -132,6 +134,35 @@ __device__ __forceinline__ bool rs_depth(const RsTri& t, const RsCam& cam, int i
 
 inline uint64_t rs_list_entries(uint32_t F, uint32_t V, uint32_t cap) {
   return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)F * V, cap));
+}
+
+// The workspace of both rasterisers (host side; the kernels take its members).
+struct RsWs {
+  uint64_t* keys;                                                // [n_keys] dns_render_mesh: one per pixel and view
+  uint32_t* counters;                                            // [RS_MAX_LAUNCHES] entries of each launch's list
+  uint64_t* list;                                                // [rs_list_entries] (triangle, view) pairs
+};
+
+// Its parts into *w; returns its bytes (ws NULL: the size only).  n_keys 0 (dns_rasterize_depth): the counters come first.
+inline size_t rs_layout(void* ws, uint64_t n_keys, uint32_t F, uint32_t V, RsWs* w) {
+  WsCarve c(ws);
+  w->keys = c.take<uint64_t>(n_keys);
+  w->counters = c.take<uint32_t>(RS_MAX_LAUNCHES);
+  w->list = c.take<uint64_t>(rs_list_entries(F, V, RS_LIST_CAP));
+  return c.end256();
+}
+
+// F faces x V views cut into n_launch launches of r triangles x g views, r g <= cap (list_cap 0: RS_LIST_CAP).
+struct RsCut {
+  uint32_t cap, r, g;
+  uint64_t n_launch;
+};
+
+inline RsCut rs_cut(uint32_t F, uint32_t V, uint32_t list_cap) {
+  const uint32_t cap = list_cap ? std::min(list_cap, RS_LIST_CAP) : RS_LIST_CAP;
+  const uint32_t r = std::max(1u, std::min(F, cap));
+  const uint32_t g = std::min(std::min(V, 65535u), std::max(1u, cap / r));
+  return {cap, r, g, F ? (uint64_t)((F + r - 1) / r) * ((V + g - 1) / g) : 0};
 }
 
 }  // namespace dns

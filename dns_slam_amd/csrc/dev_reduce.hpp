@@ -1,9 +1,9 @@
-// Wave sum and maximum, workgroup scan and workspace alignment of the mesh and evaluation kernels (mesh, mesh_cc, mesh_eval,
-// mesh_raster, mesh_masks).
+// Wave sum and maximum and workgroup scan of the mesh and evaluation kernels (mesh, mesh_cc, mesh_eval, mesh_raster,
+// mesh_masks); brings ws_carve.hpp, the HIP-free workspace alignment and carver their launch wrappers lay workspaces out with.
 #pragma once
 #include "common.hpp"
+#include "ws_carve.hpp"
 namespace dns {
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }      // workspaces are carved into 256-byte aligned parts
 // The sum over the 64 lanes, in every lane; butterfly from 32 down to 1: in floating point this order decides the bits.
 template <class T>
 __device__ __forceinline__ T wave_sum(T x) {

@@ -45,25 +45,20 @@ struct HlWs {
   uint32_t* cursor;
 };
 
-size_t hl_bytes(uint64_t N, uint64_t cap) {
-  return 3 * align256(N * 4) + align256(N * 8) + align256(cap * 32) + 2 * align256(cap * 4) + align256(HL_PARTIALS * sizeof(HlPartial)) +
-         align256(sizeof(HullPick)) + 256;
-}
-
-HlWs hl_layout(void* ws, uint64_t N, uint64_t cap) {
-  HlWs w;
-  char* p = (char*)ws;
-  w.face = (int32_t*)p, p += align256(N * 4);
-  w.ids = (int32_t*)p, p += align256(N * 4);
-  w.ids2 = (int32_t*)p, p += align256(N * 4);
-  w.best = (double*)p, p += align256(N * 8);
-  w.planes = (double*)p, p += align256(cap * 32);
-  w.deadf = (uint32_t*)p, p += align256(cap * 4);
-  w.dead_ids = (int32_t*)p, p += align256(cap * 4);
-  w.partial = (HlPartial*)p, p += align256(HL_PARTIALS * sizeof(HlPartial));
-  w.record = (HullPick*)p, p += align256(sizeof(HullPick));
-  w.cursor = (uint32_t*)p;
-  return w;
+// The parts of the workspace of N points and cap faces into *w; returns its bytes (ws NULL: the size only).
+size_t hl_layout(void* ws, uint64_t N, uint64_t cap, HlWs* w) {
+  WsCarve c(ws);
+  w->face = c.take<int32_t>(N);
+  w->ids = c.take<int32_t>(N);
+  w->ids2 = c.take<int32_t>(N);
+  w->best = c.take<double>(N);
+  w->planes = c.take<double>(cap * 4);
+  w->deadf = c.take<uint32_t>(cap);
+  w->dead_ids = c.take<int32_t>(cap);
+  w->partial = c.take<HlPartial>(HL_PARTIALS);
+  w->record = c.take<HullPick>(1);
+  w->cursor = c.take<uint32_t>(64);                              // one word used; a whole 256-byte part
+  return c.end();
 }
 
 __device__ __forceinline__ double hl_eval(const double* __restrict__ pl, double x, double y, double z) {
@@ -281,7 +276,8 @@ using namespace dns;
 
 extern "C" uint64_t dns_convex_hull_ws_bytes(uint32_t N, uint32_t face_cap) {
   if (N >= (1u << 31) || face_cap >= (1u << 28)) return 0;
-  return hl_bytes(N, face_cap);
+  HlWs w;
+  return hl_layout(nullptr, N, face_cap, &w);
 }
 
 extern "C" int dns_convex_hull(const double* points, uint32_t N, double eps, void* ws, uint32_t face_cap, int32_t* faces_out,
@@ -300,7 +296,8 @@ extern "C" int dns_convex_hull(const double* points, uint32_t N, double eps, voi
     return DNS_E_STATE;
   }
   HlBackend be;
-  be.pts = points, be.N = N, be.cap = face_cap, be.w = hl_layout(ws, N, face_cap), be.st = st, be.n_list = 0;
+  be.pts = points, be.N = N, be.cap = face_cap, be.st = st, be.n_list = 0;
+  hl_layout(ws, N, face_cap, &be.w);
   be.see = eps;                                                // hull_run raises it to eps + tau once it knows the scale
   HullResult res;
   rc = fill_words(be.w.deadf, 0u, face_cap, st, "dns_convex_hull");

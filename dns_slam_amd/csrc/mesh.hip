@@ -41,21 +41,14 @@ struct McWs {
   uint64_t* bpre;    // [n_blocks][2] exclusive prefixes of bcount
 };
 
-McWs ws_layout(void* ws, uint32_t N) {
+// The parts of N points' workspace into *w; returns its bytes (ws NULL: the size only).  The last part is not padded.
+size_t ws_layout(void* ws, uint32_t N, McWs* w) {
   const size_t n_chunks = (N + WAVE - 1) / WAVE, n_blocks = (N + MC_BLOCK - 1) / MC_BLOCK;
-  char* p = (char*)ws;
-  McWs w;
-  w.masks = (uint64_t*)p;
-  p += align256(n_chunks * 3 * sizeof(uint64_t));
-  w.bcount = (uint32_t*)p;
-  p += align256(n_blocks * 2 * sizeof(uint32_t));
-  w.bpre = (uint64_t*)p;
-  return w;
-}
-
-size_t ws_bytes(uint32_t N) {
-  const size_t n_chunks = (N + WAVE - 1) / WAVE, n_blocks = (N + MC_BLOCK - 1) / MC_BLOCK;
-  return align256(n_chunks * 3 * sizeof(uint64_t)) + align256(n_blocks * 2 * sizeof(uint32_t)) + n_blocks * 2 * sizeof(uint64_t);
+  WsCarve c(ws);
+  w->masks = c.take<uint64_t>(n_chunks * 3);
+  w->bcount = c.take<uint32_t>(n_blocks * 2);
+  w->bpre = c.take<uint64_t>(n_blocks * 2);
+  return c.end();
 }
 
 // The point's 8 cube corners (corner c at offset (c & 1, c >> 1 & 1, c >> 2 & 1)); corners outside the grid read as
@@ -276,7 +269,8 @@ using namespace dns;
 extern "C" uint64_t dns_mc_ws_bytes(uint32_t nx, uint32_t ny, uint32_t nz) {
   const uint64_t N = (uint64_t)nx * ny * nz;
   if (N == 0 || N >= (1ull << 31)) return 0;
-  return ws_bytes((uint32_t)N);
+  McWs w;
+  return ws_layout(nullptr, (uint32_t)N, &w);
 }
 
 static int mc_args(const char* who, uint32_t nx, uint32_t ny, uint32_t nz) {
@@ -296,7 +290,8 @@ extern "C" int dns_mc_count(const float* vol, uint32_t nx, uint32_t ny, uint32_t
   if (N == 0) return fill_words(totals, 0u, 4, st, "dns_mc_count");
   DNS_REQUIRE(vol && ws, "dns_mc_count: NULL argument");
   const McGrid g{nx, ny, nz, (uint32_t)N, ny * nz};
-  const McWs w = ws_layout(ws, g.N);
+  McWs w;
+  ws_layout(ws, g.N, &w);
   const uint32_t n_blocks = (g.N + MC_BLOCK - 1) / MC_BLOCK;
   DNS_LAUNCH(mc_count_kernel, dim3(n_blocks), dim3(MC_BLOCK), 0, st, vol, g, level, w);
   DNS_LAUNCH(mc_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, w, n_blocks, totals);
@@ -319,7 +314,8 @@ extern "C" int dns_mc_emit(const float* vol, uint32_t nx, uint32_t ny, uint32_t 
   DNS_REQUIRE(v_cap == 0 || verts, "dns_mc_emit: NULL verts with v_cap > 0");
   DNS_REQUIRE(f_cap == 0 || faces, "dns_mc_emit: NULL faces with f_cap > 0");
   const McGrid g{nx, ny, nz, (uint32_t)N, ny * nz};
-  const McWs w = ws_layout(const_cast<void*>(ws), g.N);
+  McWs w;
+  ws_layout(const_cast<void*>(ws), g.N, &w);
   hipStream_t st = (hipStream_t)stream;
   DNS_LAUNCH(mc_emit_kernel, dim3((g.N + MC_BLOCK - 1) / MC_BLOCK), dim3(MC_BLOCK), 0, st, vol, g, level, o, s, w, verts, v_cap,
              faces, f_cap);

@@ -45,24 +45,15 @@ struct CcWs {
   uint32_t cap;      // 4 F
 };
 
-CcWs ws_layout(void* ws, uint32_t F) {
-  CcWs w;
-  w.cap = 4u * F;
-  char* p = (char*)ws;
-  w.keys = (uint64_t*)p;
-  p += align256((size_t)w.cap * sizeof(uint64_t));
-  w.count = (uint32_t*)p;
-  p += align256((size_t)w.cap * sizeof(uint32_t));
-  w.holder = (int32_t*)p;
-  p += align256((size_t)w.cap * 2 * sizeof(int32_t));
-  w.parent = (int32_t*)p;
-  return w;
-}
-
-size_t ws_bytes(uint32_t F) {
-  const size_t cap = 4 * (size_t)F;
-  return align256(cap * sizeof(uint64_t)) + align256(cap * sizeof(uint32_t)) + align256(cap * 2 * sizeof(int32_t)) +
-         (size_t)F * sizeof(int32_t);
+// The parts of F faces' workspace into *w; returns its bytes (ws NULL: the size only).  The last part is not padded.
+size_t ws_layout(void* ws, uint32_t F, CcWs* w) {
+  WsCarve c(ws);
+  w->cap = 4u * F;
+  w->keys = c.take<uint64_t>(w->cap);
+  w->count = c.take<uint32_t>(w->cap);
+  w->holder = c.take<int32_t>(2ull * w->cap);
+  w->parent = c.take<int32_t>(F);
+  return c.end();
 }
 
 __global__ __launch_bounds__(CC_BLOCK) void cc_init_kernel(CcWs ws, uint32_t F, double* __restrict__ comp_area,
@@ -216,7 +207,8 @@ using namespace dns;
 
 extern "C" uint64_t dns_mesh_cc_ws_bytes(uint32_t F) {
   if (F == 0 || F >= (1u << 29)) return 0;
-  return ws_bytes(F);
+  CcWs w;
+  return ws_layout(nullptr, F, &w);
 }
 
 extern "C" int dns_mesh_components(const float* verts, uint32_t V, const int32_t* faces, uint32_t F, void* ws, int32_t* comp,
@@ -227,7 +219,8 @@ extern "C" int dns_mesh_components(const float* verts, uint32_t V, const int32_t
   DNS_REQUIRE(faces && ws && comp && comp_area && status, "dns_mesh_components: NULL argument");
   DNS_REQUIRE(V == 0 || verts, "dns_mesh_components: NULL verts with V > 0");
   hipStream_t st = (hipStream_t)stream;
-  const CcWs w = ws_layout(ws, F);
+  CcWs w;
+  ws_layout(ws, F, &w);
   const auto blocks = [](uint64_t n) { return dim3((uint32_t)((n + CC_BLOCK - 1) / CC_BLOCK)); };
   DNS_LAUNCH(cc_init_kernel, blocks(w.cap), dim3(CC_BLOCK), 0, st, w, F, comp_area, status);
   DNS_LAUNCH(cc_edges_kernel, blocks(3ull * F), dim3(CC_BLOCK), 0, st, faces, F, V, w, status);

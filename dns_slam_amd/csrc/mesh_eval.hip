@@ -76,30 +76,25 @@ inline uint32_t cells_target(uint32_t M) {
   return (uint32_t)(t < 1 ? 1 : (t > NN_CELLS_CAP ? NN_CELLS_CAP : t));
 }
 
+// The nearest-point parts of M reference points and N queries, taken from c into *w (icp_layout goes on from there).
+void nn_take(WsCarve& c, uint32_t M, uint32_t N, NnWs* w) {
+  w->target = cells_target(M);
+  w->cells_alloc = (w->target + NN_SCAN_TILE - 1) / NN_SCAN_TILE * NN_SCAN_TILE;
+  w->head = c.take<NnHeader>(1);
+  w->count = c.take<uint32_t>((uint64_t)w->cells_alloc + 1);
+  w->start = c.take<uint32_t>((uint64_t)w->cells_alloc + 1);
+  w->sums = c.take<uint32_t>(1024);
+  w->point_cell = c.take<uint32_t>(M);
+  w->sorted = c.take<float4>(M);
+  w->todo = c.take<uint32_t>(N);
+  w->best = c.take<uint64_t>(N);
+}
+
+// dns_nearest_points' workspace into *w; returns its bytes (ws NULL: the size only).
 size_t nn_layout(void* ws, uint32_t M, uint32_t N, NnWs* w) {
-  const uint32_t target = cells_target(M);
-  const uint32_t alloc = (target + NN_SCAN_TILE - 1) / NN_SCAN_TILE * NN_SCAN_TILE;
-  char* p = (char*)ws;
-  size_t off = 0;
-  const auto take = [&](size_t bytes) {
-    char* r = p + off;
-    off += align256(bytes);
-    return r;
-  };
-  char* head = take(sizeof(NnHeader));
-  char* count = take(((size_t)alloc + 1) * 4);
-  char* start = take(((size_t)alloc + 1) * 4);
-  char* sums = take(1024 * 4);
-  char* pc = take((size_t)M * 4);
-  char* sorted = take((size_t)M * 16);
-  char* todo = take((size_t)N * 4);
-  char* best = take((size_t)N * 8);
-  if (w) {
-    w->head = (NnHeader*)head, w->count = (uint32_t*)count, w->start = (uint32_t*)start, w->sums = (uint32_t*)sums;
-    w->point_cell = (uint32_t*)pc, w->sorted = (float4*)sorted, w->todo = (uint32_t*)todo, w->best = (uint64_t*)best;
-    w->target = target, w->cells_alloc = alloc;
-  }
-  return off;
+  WsCarve c(ws);
+  nn_take(c, M, N, w);
+  return c.end256();
 }
 
 __device__ __forceinline__ uint32_t f2ord(float f) {
@@ -611,16 +606,22 @@ __global__ __launch_bounds__(NN_BLOCK) void icp_solve_kernel(const double* __res
   for (int k = 0; k < ICP_SUMS; ++k) result[21 + k] = sum[k];
 }
 
-size_t icp_layout(void* ws, uint32_t M, uint32_t N, NnWs* w, IcpState** state, float** xf, double** partial) {
-  size_t off = nn_layout(ws, M, N, w);
-  char* p = (char*)ws;
-  if (state) *state = (IcpState*)(p + off);
-  off += align256(sizeof(IcpState));
-  if (xf) *xf = (float*)(p + off);
-  off += align256((size_t)N * 12);
-  if (partial) *partial = (double*)(p + off);
-  off += align256((size_t)ICP_ROWS * ICP_SUMS * 8);
-  return off;
+// dns_icp_point_to_point's workspace (host side only; the kernels take its members): the nearest-point parts, then its own three.
+struct IcpWs {
+  NnWs nn;
+  IcpState* state;
+  float* xf;             // [N][3] the transformed source points of the pass
+  double* partial;       // [ICP_ROWS][ICP_SUMS]
+};
+
+// Its parts into *w; returns its bytes (ws NULL: the size only).
+size_t icp_layout(void* ws, uint32_t M, uint32_t N, IcpWs* w) {
+  WsCarve c(ws);
+  nn_take(c, M, N, &w->nn);
+  w->state = c.take<IcpState>(1);
+  w->xf = c.take<float>(3ull * N);
+  w->partial = c.take<double>((uint64_t)ICP_ROWS * ICP_SUMS);
+  return c.end256();
 }
 
 // ---- frustum test --------------------------------------------------------------------------------------------------------
@@ -660,7 +661,8 @@ using namespace dns;
 
 extern "C" uint64_t dns_nearest_ws_bytes(uint32_t M, uint32_t N) {
   if (M >= (1u << 31) || N >= (1u << 31)) return 0;
-  return nn_layout(nullptr, M, N, nullptr);
+  NnWs w;
+  return nn_layout(nullptr, M, N, &w);
 }
 
 namespace {
@@ -721,7 +723,8 @@ extern "C" int dns_nearest_points(const float* ref, uint32_t M, const float* que
 
 extern "C" uint64_t dns_icp_ws_bytes(uint32_t M, uint32_t N) {
   if (M >= (1u << 31) || N >= (1u << 31) || M == 0 || N == 0) return 0;
-  return icp_layout(nullptr, M, N, nullptr, nullptr, nullptr, nullptr);
+  IcpWs w;
+  return icp_layout(nullptr, M, N, &w);
 }
 
 extern "C" int dns_icp_point_to_point(const float* src, uint32_t N, const float* tgt, uint32_t M, const double* init, float max_dist,
@@ -741,25 +744,22 @@ extern "C" int dns_icp_point_to_point(const float* src, uint32_t N, const float*
     DNS_REQUIRE(t0.m[k] - t0.m[k] == 0.0, "dns_icp_point_to_point: init[%d] is not finite", k);
   }
   hipStream_t st = (hipStream_t)stream;
-  NnWs w;
-  IcpState* state;
-  float* xf;
-  double* partial;
-  icp_layout(ws, M, N, &w, &state, &xf, &partial);
+  IcpWs w;
+  icp_layout(ws, M, N, &w);
   // at or above every d2 whose fp32 root is <= max_dist (2^-21 covers the rounding of the square and of the root)
   const double md2 = (double)max_dist * (double)max_dist * (1.0 + 0x1p-21);
   const float stop_d2 = md2 < 3.0e38 ? (float)md2 : __builtin_inff();
   const uint32_t rows = std::min(ICP_ROWS, (N + NN_BLOCK - 1) / NN_BLOCK);
-  nn_launch_box(w, true, tgt, M, src, N, status, st);
-  nn_launch_build(w, tgt, M, status, st);
-  DNS_LAUNCH(icp_begin_kernel, dim3(1), dim3(1), 0, st, state, t0, status, result);
+  nn_launch_box(w.nn, true, tgt, M, src, N, status, st);
+  nn_launch_build(w.nn, tgt, M, status, st);
+  DNS_LAUNCH(icp_begin_kernel, dim3(1), dim3(1), 0, st, w.state, t0, status, result);
   for (uint32_t pass = 0; pass <= max_iter; ++pass) {
-    DNS_LAUNCH(icp_query_kernel, nn_blocks(N), dim3(NN_BLOCK), 0, st, w, M, src, N, max_ring, stop_d2, state, xf);
-    nn_launch_brute(w, M, xf, N, (const uint32_t*)state->qst, st);
-    DNS_LAUNCH(icp_reduce_kernel, dim3(rows), dim3(NN_BLOCK), 0, st, w, tgt, M, (const float*)xf, N, max_dist,
-               (const IcpState*)state, partial);
-    DNS_LAUNCH(icp_solve_kernel, dim3(1), dim3(NN_BLOCK), 0, st, (const double*)partial, rows, N, pass, max_iter, rel_fitness,
-               rel_rmse, state, result, status);
+    DNS_LAUNCH(icp_query_kernel, nn_blocks(N), dim3(NN_BLOCK), 0, st, w.nn, M, src, N, max_ring, stop_d2, w.state, w.xf);
+    nn_launch_brute(w.nn, M, w.xf, N, (const uint32_t*)w.state->qst, st);
+    DNS_LAUNCH(icp_reduce_kernel, dim3(rows), dim3(NN_BLOCK), 0, st, w.nn, tgt, M, (const float*)w.xf, N, max_dist,
+               (const IcpState*)w.state, w.partial);
+    DNS_LAUNCH(icp_solve_kernel, dim3(1), dim3(NN_BLOCK), 0, st, (const double*)w.partial, rows, N, pass, max_iter, rel_fitness,
+               rel_rmse, w.state, result, status);
   }
   return check_launch("dns_icp_point_to_point");
 }

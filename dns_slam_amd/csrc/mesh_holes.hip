@@ -204,7 +204,7 @@ using namespace dns;
 
 extern "C" uint64_t dns_mesh_holes_ws_bytes(uint32_t F, uint32_t V) {
   Plan p;
-  if (F == 0 || !make_plan(F, V, align256, &p)) return 0;
+  if (F == 0 || !make_plan(F, V, &p)) return 0;
   return p.bytes;
 }
 
@@ -218,7 +218,7 @@ extern "C" int dns_mesh_holes_count(const int32_t* faces, uint32_t F, uint32_t V
   if (F == 0) return fill_words(info, 0u, INFO_WORDS, st, "dns_mesh_holes_count");
   DNS_REQUIRE(faces && ws, "dns_mesh_holes_count: NULL argument");
   Plan p;
-  make_plan(F, V, align256, &p);
+  make_plan(F, V, &p);
   const HolesWs w = ws_layout(ws, p);
   DNS_LAUNCH(holes_init_kernel, dim3(p.grid_init), dim3(HOLES_BLOCK), 0, st, w, V, info);
   DNS_LAUNCH(holes_edges_kernel, dim3(p.grid_edges), dim3(HOLES_BLOCK), 0, st, faces, F, V, w, info);
@@ -234,7 +234,7 @@ extern "C" int dns_mesh_holes_emit(const void* ws, uint32_t V, uint32_t max_edge
   if (V == 0) return DNS_OK;
   DNS_REQUIRE(ws && new_faces, "dns_mesh_holes_emit: NULL argument");
   Plan p;
-  vertex_plan(V, align256, &p);
+  vertex_plan(V, &p);
   const HolesWs w = ws_vertex_parts((void*)ws, p);
   DNS_LAUNCH(holes_emit_kernel, dim3(p.grid_verts), dim3(HOLES_BLOCK), 0, (hipStream_t)stream, w, V, max_edges, new_faces);
   return check_launch("dns_mesh_holes_emit");

@@ -1,8 +1,7 @@
 // Workspace layout and grid sizes of the mesh hole filling (mesh_holes.hip), free of HIP headers: tools/mesh_holes_plan_check.cpp
 // walks it on the host under ASan + UBSan.
 //
-// The parts, in this order, each a multiple of the alignment the caller's `align` gives (mesh_holes.hip passes dev_reduce.hpp's
-// align256, which cannot be included here because it brings the HIP headers):
+// The parts, in this order, each padded to a multiple of 256 bytes (ws_carve.hpp's align256):
 //   n_out, n_in, next, cnt   [V] uint32 each: the per-vertex words
 //   bcount, bpre             [v_blocks][2] uint32 each: (faces, loops) of a workgroup of HOLES_BLOCK vertices and their exclusive
 //                            prefixes -- the scan's carries
@@ -11,6 +10,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "ws_carve.hpp"
 
 namespace dns {
 namespace holesp {
@@ -35,17 +35,16 @@ struct Plan {
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + HOLES_BLOCK - 1) / HOLES_BLOCK); }
 
 // The per-vertex parts and the carries of V vertices (F plays no part).
-template <class Align>
-inline void vertex_plan(uint32_t V, Align align, Plan* p) {
+inline void vertex_plan(uint32_t V, Plan* p) {
   p->V = V;
   p->v_blocks = blocks_for(V);
   uint64_t o = 0;
-  const uint64_t words = (uint64_t)align((size_t)V * sizeof(uint32_t));
+  const uint64_t words = (uint64_t)align256((size_t)V * sizeof(uint32_t));
   p->off_n_out = o, o += words;
   p->off_n_in = o, o += words;
   p->off_next = o, o += words;
   p->off_cnt = o, o += words;
-  const uint64_t carries = (uint64_t)align((size_t)p->v_blocks * 2 * sizeof(uint32_t));
+  const uint64_t carries = (uint64_t)align256((size_t)p->v_blocks * 2 * sizeof(uint32_t));
   p->off_bcount = o, o += carries;
   p->off_bpre = o, o += carries;
   p->vertex_bytes = o;
@@ -53,16 +52,15 @@ inline void vertex_plan(uint32_t V, Align align, Plan* p) {
 }
 
 // false: a refused size (F >= 2^29, V >= 2^31).  F = 0 gives a plan of the vertex parts alone, which nobody launches on.
-template <class Align>
-inline bool make_plan(uint32_t F, uint32_t V, Align align, Plan* p) {
+inline bool make_plan(uint32_t F, uint32_t V, Plan* p) {
   if (F >= MAX_FACES || V >= MAX_VERTS) return false;
-  vertex_plan(V, align, p);
+  vertex_plan(V, p);
   p->F = F;
   p->cap = 4u * F;
   uint64_t o = p->vertex_bytes;
-  p->off_keys = o, o += (uint64_t)align((size_t)p->cap * sizeof(uint64_t));
-  p->off_count = o, o += (uint64_t)align((size_t)p->cap * sizeof(uint32_t));
-  p->off_holder = o, o += (uint64_t)align((size_t)p->cap * sizeof(uint32_t));
+  p->off_keys = o, o += (uint64_t)align256((size_t)p->cap * sizeof(uint64_t));
+  p->off_count = o, o += (uint64_t)align256((size_t)p->cap * sizeof(uint32_t));
+  p->off_holder = o, o += (uint64_t)align256((size_t)p->cap * sizeof(uint32_t));
   p->bytes = o;
   p->grid_edges = blocks_for(3ull * F);
   p->grid_slots = blocks_for(p->cap);

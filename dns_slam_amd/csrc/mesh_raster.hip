@@ -192,7 +192,8 @@ using namespace dns;
 
 extern "C" uint64_t dns_rasterize_ws_bytes(uint32_t F, uint32_t V, uint32_t H, uint32_t W) {
   if (F >= (1u << 31) || H == 0 || W == 0 || H > 32768u || W > 32768u) return 0;
-  return align256((size_t)RS_MAX_LAUNCHES * 4) + align256(rs_list_entries(F, V, RS_LIST_CAP) * 8);
+  RsWs w;
+  return rs_layout(nullptr, 0, F, V, &w);
 }
 
 extern "C" int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t* faces, uint32_t F, const float* w2c, uint32_t V,
@@ -208,35 +209,31 @@ extern "C" int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t
   DNS_REQUIRE(F == 0 || (verts && faces), "dns_rasterize_depth: F > 0 needs verts and faces");
   DNS_REQUIRE(intr[0] - intr[0] == 0.f && intr[1] - intr[1] == 0.f && intr[0] != 0.f && intr[1] != 0.f && intr[2] - intr[2] == 0.f &&
                   intr[3] - intr[3] == 0.f, "dns_rasterize_depth: intrinsics must be finite, fx and fy non-zero");
-  const uint32_t cap = list_cap ? std::min(list_cap, RS_LIST_CAP) : RS_LIST_CAP;
-  // launches of r triangles x g views, r g <= cap
-  const uint32_t r = std::max(1u, std::min(F, cap));
-  const uint32_t g = std::min(std::min(V, 65535u), std::max(1u, cap / r));
-  const uint64_t n_launch = F ? (uint64_t)((F + r - 1) / r) * ((V + g - 1) / g) : 0;
+  const auto [cap, r, g, n_launch] = rs_cut(F, V, list_cap);
   DNS_REQUIRE(n_launch <= RS_MAX_LAUNCHES, "dns_rasterize_depth: list_cap %u cuts %u faces x %u views into %llu launches (at most %u)",
               list_cap, F, V, (unsigned long long)n_launch, RS_MAX_LAUNCHES);
   hipStream_t st = (hipStream_t)stream;
-  uint32_t* counters = (uint32_t*)ws;
-  uint64_t* list = (uint64_t*)((char*)ws + align256((size_t)RS_MAX_LAUNCHES * 4));
+  RsWs w;
+  rs_layout(ws, 0, F, V, &w);
   uint32_t* img = (uint32_t*)depth;
   const size_t n_words = (size_t)V * H * W;
   const RsCam cam = {intr[0], intr[1], intr[2], intr[3], z_near, z_far, (int)H, (int)W};
   const uint32_t fill_grid = (uint32_t)std::min<size_t>(8192, (n_words + RS_BLOCK - 1) / RS_BLOCK);
   DNS_LAUNCH(rs_init_kernel, dim3(std::max(fill_grid, (uint32_t)((n_launch + RS_BLOCK - 1) / RS_BLOCK))), dim3(RS_BLOCK), 0, st, img,
-             n_words, counters, (uint32_t)n_launch, status);
+             n_words, w.counters, (uint32_t)n_launch, status);
   uint32_t k = 0;
   for (uint32_t v_lo = 0; F && v_lo < V; v_lo += g) {
     const uint32_t nv = std::min(g, V - v_lo);
     for (uint32_t f_lo = 0; f_lo < F; f_lo += r, ++k) {
       const uint32_t f_hi = std::min(F, f_lo + r);
       DNS_LAUNCH(rs_setup_kernel, dim3((f_hi - f_lo + RS_BLOCK - 1) / RS_BLOCK, nv), dim3(RS_BLOCK), 0, st, verts, P, faces, f_lo, f_hi,
-                 w2c, v_lo, cam, flags, list, cap, counters + k, img, status);
+                 w2c, v_lo, cam, flags, w.list, cap, w.counters + k, img, status);
       if (!(flags & DNS_RASTER_SIMPLE))
-        DNS_LAUNCH(rs_large_kernel, dim3(RS_LARGE_GRID), dim3(RS_BLOCK), 0, st, verts, P, faces, F, w2c, V, cam, (const uint64_t*)list,
-                   cap, (const uint32_t*)(counters + k), img, status);
+        DNS_LAUNCH(rs_large_kernel, dim3(RS_LARGE_GRID), dim3(RS_BLOCK), 0, st, verts, P, faces, F, w2c, V, cam, (const uint64_t*)w.list,
+                   cap, (const uint32_t*)(w.counters + k), img, status);
     }
   }
-  DNS_LAUNCH(rs_finish_kernel, dim3(fill_grid), dim3(RS_BLOCK), 0, st, img, n_words, (const uint32_t*)counters, (uint32_t)n_launch, status);
+  DNS_LAUNCH(rs_finish_kernel, dim3(fill_grid), dim3(RS_BLOCK), 0, st, img, n_words, (const uint32_t*)w.counters, (uint32_t)n_launch, status);
   return check_launch("dns_rasterize_depth");
 }
 

@@ -925,6 +925,13 @@ def feature_gather(pts: torch.Tensor, refer_w2c: torch.Tensor, K, feat_nhwc: tor
     return code, mask.bool()
 
 
+def _byte_workspace(n_bytes, dev, refusal: str) -> torch.Tensor:
+    """The uint8 workspace of n_bytes (a dns_*_ws_bytes value) on dev; 0 bytes is that function's refusal: ValueError(refusal)."""
+    if int(n_bytes) == 0:
+        raise ValueError(refusal)
+    return torch.empty(int(n_bytes), dtype=torch.uint8, device=dev)
+
+
 # ----------------------------------------------------------------------------- mesh extraction (csrc/mesh.hip)
 def marching_cubes(volume: torch.Tensor, level: float, origin, spacing):
     """volume [nx, ny, nz] fp32 (C order; volume[i,j,k] at origin + (i,j,k) * spacing), level, origin / spacing 3 floats each
@@ -1316,10 +1323,7 @@ def mesh_components(verts: torch.Tensor, faces: torch.Tensor):
     comp_area = torch.empty(F, dtype=torch.float64, device=dev)
     if F == 0:
         return comp, comp_area, 0
-    ws_b = int(_rawlib.dns_mesh_cc_ws_bytes(F))
-    if ws_b == 0:
-        raise ValueError(f"mesh_components: {F} faces are too many (>= 2^29)")
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws = _byte_workspace(_rawlib.dns_mesh_cc_ws_bytes(F), dev, f"mesh_components: {F} faces are too many (>= 2^29)")
     status = torch.empty(2, dtype=torch.int32, device=dev)
     check(lib.dns_mesh_components(ptr(v), V, ptr(f), F, ptr(ws), ptr(comp), ptr(comp_area), ptr(status), stream_ptr()),
           "dns_mesh_components")
@@ -1362,10 +1366,7 @@ def mesh_fill_holes(faces: torch.Tensor, n_verts: int, max_edges: int = HOLES_MA
         info["watertight"] = True
         return faces, info
     dev = f.device
-    ws_b = int(_rawlib.dns_mesh_holes_ws_bytes(F, V))
-    if ws_b == 0:
-        raise ValueError(f"mesh_fill_holes: {F} faces are too many (>= 2^29)")
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws = _byte_workspace(_rawlib.dns_mesh_holes_ws_bytes(F, V), dev, f"mesh_fill_holes: {F} faces are too many (>= 2^29)")
     info_d = torch.empty(8, dtype=torch.int32, device=dev)
     check(lib.dns_mesh_holes_count(ptr(f), F, V, max_edges, ptr(ws), ptr(info_d), stream_ptr()), "dns_mesh_holes_count")
     words = [int(x) for x in info_d.cpu().tolist()]
@@ -1404,12 +1405,9 @@ def nearest_points_launch(ref: torch.Tensor, query: torch.Tensor, method: str = 
     if M == 0:
         raise ValueError(f"nearest_points: no reference points for {N} queries")
     dev = q.device
-    ws_b = int(_rawlib.dns_nearest_ws_bytes(M, N))
-    if ws_b == 0:
-        raise ValueError(f"nearest_points: {M} reference points / {N} queries are too many (>= 2^31)")
+    ws = _byte_workspace(_rawlib.dns_nearest_ws_bytes(M, N), dev, f"nearest_points: {M} reference points / {N} queries are too many (>= 2^31)")
     dist = torch.empty(N, dtype=torch.float32, device=dev)
     idx = torch.empty(N, dtype=torch.int32, device=dev)
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
     status = torch.empty(4, dtype=torch.int32, device=dev)
     check(lib.dns_nearest_points(ptr(r), M, ptr(q), N, int(max_rings), 1 if method == "brute" else 0, ptr(ws), ptr(dist),
                                  ptr(idx), ptr(status), stream_ptr()), "dns_nearest_points")
@@ -1471,11 +1469,8 @@ def icp_point_to_point_launch(source: torch.Tensor, target: torch.Tensor, max_di
     host reads)."""
     s, t, md, t0 = _icp_arguments(source, target, max_dist, init, max_iter, relative_fitness, relative_rmse)
     N, M = int(s.shape[0]), int(t.shape[0])
-    ws_b = int(_rawlib.dns_icp_ws_bytes(M, N))
-    if ws_b == 0:
-        raise ValueError(f"icp_point_to_point: {N} source / {M} target points are too many (>= 2^31)")
     dev = s.device
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws = _byte_workspace(_rawlib.dns_icp_ws_bytes(M, N), dev, f"icp_point_to_point: {N} source / {M} target points are too many (>= 2^31)")
     result = torch.empty(38, dtype=torch.float64, device=dev)
     status = torch.empty(4, dtype=torch.int32, device=dev)
     check(lib.dns_icp_point_to_point(ptr(s), N, ptr(t), M, t0, md, int(max_iter), float(relative_fitness), float(relative_rmse),
@@ -1593,11 +1588,9 @@ def ms_ssim_launch(pred: torch.Tensor, gt: torch.Tensor, depth: Optional[torch.T
     p, g, d, _, F, H, W = _ms_ssim_arguments(pred, gt, depth)
     if method == "torch":
         return _ms_ssim_torch(p.view(F, H, W, 3), g.view(F, H, W, 3), None if d is None else d.view(F, H, W), F, H, W)
-    ws_b = int(_rawlib.dns_ms_ssim_ws_bytes(F, H, W))
-    if ws_b == 0:
-        raise ValueError(f"ms_ssim: {F} frames of {H} x {W} are refused (at most 65535 frames, sides <= 32768)")
     dev = p.device
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws = _byte_workspace(_rawlib.dns_ms_ssim_ws_bytes(F, H, W), dev,
+                         f"ms_ssim: {F} frames of {H} x {W} are refused (at most 65535 frames, sides <= 32768)")
     val = torch.empty(F, dtype=torch.float64, device=dev)
     mse = torch.empty(F, dtype=torch.float64, device=dev)
     n_valid = torch.empty(F, dtype=torch.int64, device=dev)
@@ -1706,10 +1699,8 @@ def rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near=0.01,
     status = torch.zeros(4, dtype=torch.int32, device=dev)
     if V == 0:
         return depth, status
-    ws_b = int(_rawlib.dns_rasterize_ws_bytes(F, V, int(H), int(W)))
-    if ws_b == 0:
-        raise ValueError(f"rasterize_depth: {F} faces at {H} x {W} are refused (F >= 2^31)")
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws = _byte_workspace(_rawlib.dns_rasterize_ws_bytes(F, V, int(H), int(W)), dev,
+                         f"rasterize_depth: {F} faces at {H} x {W} are refused (F >= 2^31)")
     flags = (1 if method == "simple" else 0) | (2 if stats else 0)
     check(lib.dns_rasterize_depth(ptr(v), P, ptr(f), F, ptr(w), V, int(H), int(W), _intrinsics(fx, fy, cx, cy), zn, zf, flags, int(list_cap), ptr(ws),
                                   ptr(depth), ptr(status), stream_ptr()), "dns_rasterize_depth")
@@ -1832,10 +1823,7 @@ def render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, *, z_nea
            "status": torch.zeros(4, dtype=torch.int32, device=dev)}
     if V == 0:
         return out
-    ws_b = int(_rawlib.dns_render_mesh_ws_bytes(F, V, H, W))
-    if ws_b == 0:
-        raise ValueError(f"{who}: {F} faces at {H} x {W} are refused (F >= 2^31)")
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws = _byte_workspace(_rawlib.dns_render_mesh_ws_bytes(F, V, H, W), dev, f"{who}: {F} faces at {H} x {W} are refused (F >= 2^31)")
     flags = (1 if method == "simple" else 0) | (2 if stats else 0) | _RENDER_CULL_FLAGS[cull] | (_RENDER_HEADLIGHT if shade else 0)
     check(lib.dns_render_mesh(ptr(v), P, ptr(f), F, ptr(col), ptr(pts), ptr(pcol), N, int(point_size), ptr(w), V, H, W,
                               _intrinsics(fx, fy, cx, cy), zn, zf, flags, amb, (C.c_float * 3)(*bg), int(list_cap or 0), ptr(ws),
@@ -2020,10 +2008,8 @@ def convex_hull_launch(points: torch.Tensor, eps: float = 0.0, face_cap: Optiona
         raise ValueError(f"convex_hull: face_cap must be >= 4, got {cap}")
     st = stream_ptr()
     while True:
-        ws_b = int(_rawlib.dns_convex_hull_ws_bytes(N, cap))
-        if ws_b == 0:
-            raise ValueError(f"convex_hull: the hull of points needs more than {cap} faces")
-        ws = torch.empty(ws_b, dtype=torch.uint8, device=pts.device)
+        ws = _byte_workspace(_rawlib.dns_convex_hull_ws_bytes(N, cap), pts.device,
+                             f"convex_hull: the hull of points needs more than {cap} faces")
         faces = np.empty((cap, 3), np.int32)
         planes = np.empty((cap, 4), np.float64)
         nf = C.c_uint32(0)

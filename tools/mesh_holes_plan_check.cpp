@@ -13,8 +13,6 @@
 //   (d) the grids cover 3F face edges, 4F slots and V vertices with fewer than 2^31 workgroups of 256, the initialising grid
 //       covers slots, vertices and the info words, the carries hold one entry per workgroup of vertices, and the largest
 //       face-edge id 3F - 1 and slot 4F - 1 fit 31 bits.
-// The alignment is passed in as mesh_holes.hip passes dev_reduce.hpp's align256 (that header brings the HIP headers, so it is
-// restated here in one line).
 #include <stdio.h>
 #include <stdint.h>
 #include <stddef.h>
@@ -22,8 +20,6 @@
 #include "../dns_slam_amd/csrc/mesh_holes_plan.hpp"
 
 using namespace dns::holesp;
-
-static size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 static long g_fail = 0, g_plans = 0;
 #define CHECK(cond, ...)                 \
@@ -50,7 +46,7 @@ static std::vector<uint32_t> sizes(uint32_t limit_log2) {
 
 static void check(uint32_t F, uint32_t V) {
   Plan p;
-  const bool ok = make_plan(F, V, align256, &p);
+  const bool ok = make_plan(F, V, &p);
   CHECK(ok == (F < MAX_FACES && V < MAX_VERTS), "F %u V %u: planned %d", F, V, (int)ok);
   if (!ok) return;
   ++g_plans;
@@ -68,7 +64,7 @@ static void check(uint32_t F, uint32_t V) {
   }
   CHECK(p.vertex_bytes == p.off_keys && p.bytes < (1ull << 40), "F %u V %u: %llu bytes", F, V, (unsigned long long)p.bytes);
   Plan q;
-  vertex_plan(V, align256, &q);
+  vertex_plan(V, &q);
   CHECK(q.off_n_out == p.off_n_out && q.off_n_in == p.off_n_in && q.off_next == p.off_next && q.off_cnt == p.off_cnt &&
             q.off_bcount == p.off_bcount && q.off_bpre == p.off_bpre && q.vertex_bytes == p.vertex_bytes &&
             q.v_blocks == p.v_blocks && q.grid_verts == p.grid_verts,
