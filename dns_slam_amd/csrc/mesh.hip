@@ -116,26 +116,12 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_count_kernel(const float* __restr
   }
 }
 
-// One workgroup of 1024: thread t sums a contiguous run of blocks, an LDS scan of the 1024 run sums, then the run's prefixes.
-constexpr int SCAN_THREADS = 1024;
-struct McCounts {
-  uint64_t v, t;     // vertices, triangles
-  __device__ McCounts& operator+=(const McCounts& o) { return v += o.v, t += o.t, *this; }
-};
+// One workgroup: dev_reduce.hpp's carry scan of the block counts into uint64 prefixes; the two totals go into totals[0..1].
+using McCounts = Counts2<uint64_t>;      // a = vertices, b = triangles
 __global__ __launch_bounds__(SCAN_THREADS) void mc_scan_kernel(McWs ws, uint32_t n_blocks, uint64_t* __restrict__ totals) {
   __shared__ McCounts s[SCAN_THREADS];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (n_blocks + SCAN_THREADS - 1) / SCAN_THREADS;
-  const uint32_t b0 = min(t * per, n_blocks), b1 = min(b0 + per, n_blocks);
-  McCounts own{0, 0};
-  for (uint32_t b = b0; b < b1; ++b) own.v += ws.bcount[2 * b], own.t += ws.bcount[2 * b + 1];
-  const McCounts incl = block_scan_inclusive<SCAN_THREADS>(s, own);
-  uint64_t pv = incl.v - own.v, pt = incl.t - own.t;
-  for (uint32_t b = b0; b < b1; ++b) {
-    ws.bpre[2 * b] = pv, ws.bpre[2 * b + 1] = pt;
-    pv += ws.bcount[2 * b], pt += ws.bcount[2 * b + 1];
-  }
-  if (t == SCAN_THREADS - 1) totals[0] = incl.v, totals[1] = incl.t;
+  const McCounts tot = carry_scan(s, ws.bcount, ws.bpre, n_blocks);
+  if (threadIdx.x == SCAN_THREADS - 1) totals[0] = tot.a, totals[1] = tot.b;
 }
 
 // rank of grid edge (q, axis) among the crossing edges = its vertex index

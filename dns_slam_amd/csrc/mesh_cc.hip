@@ -4,9 +4,8 @@
 //
 // Four plain launches after an initialising one; no workgroup waits on another:
 //   cc_init:    edge table empty, parent[f] = f, comp_area = 0, status = 0.
-//   cc_edges:   thread = one of the 3F face edges.  The 64-bit key (min << 32 | max) claims a slot of an open-addressing
-//               table (linear probing, 4F slots for at most 3F keys) with a 64-bit compare-and-swap against the all-ones
-//               word, which no key equals (indices are below 2^31).  A returning add on the slot's counter orders the
+//   cc_edges:   thread = one of the 3F face edges.  The 64-bit key (min << 32 | max) claims a slot of dev_keytable.hpp's
+//               open-addressing table (4F slots for at most 3F keys).  A returning add on the slot's counter orders the
 //               holders; the first two leave their face id.
 //   cc_union:   thread = slot.  A slot with exactly two holders unions them in a lock-free union-find over parent[F]:
 //               find with path halving, the larger root hooked under the smaller one by compare-and-swap.  parent[x] <= x
@@ -23,6 +22,7 @@
 // A vertex index outside [0, V) is never dereferenced: it sets status[1] and the face contributes no edge and no area.
 // Compiled with -ffp-contract=off (Makefile): the area is the float64 expression tests/mesh_cc_ref.py evaluates.
 #include "common.hpp"
+#include "dev_keytable.hpp"
 #include "dev_reduce.hpp"
 
 namespace dns {
@@ -30,7 +30,6 @@ namespace dns {
 namespace {
 
 constexpr int CC_BLOCK = 256;
-constexpr uint64_t CC_EMPTY = ~0ull;
 constexpr uint32_t CC_BAD_INDEX = 1u;      // status[1] bits
 constexpr uint32_t CC_TABLE_FULL = 2u;     // cannot happen with 4F slots; checked rather than assumed
 constexpr int CC_FLAT_BLOCK = 1024;        // cc_flatten: 16 waves merge their first sums through LDS
@@ -38,7 +37,7 @@ constexpr int CC_FLAT_WAVES = CC_FLAT_BLOCK / WAVE;
 constexpr int CC_AGG_ROUNDS = 4;           // distinct roots summed per wave before the rest add on their own
 
 struct CcWs {
-  uint64_t* keys;    // [cap] edge key, CC_EMPTY = free
+  uint64_t* keys;    // [cap] edge key, KEY_EMPTY = free
   uint32_t* count;   // [cap] holders of the key
   int32_t* holder;   // [cap][2] the first two holders
   int32_t* parent;   // [F]
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(CC_BLOCK) void cc_init_kernel(CcWs ws, uint32_t F, 
                                                            uint32_t* __restrict__ status) {
   const uint32_t t = blockIdx.x * CC_BLOCK + threadIdx.x;
   if (t < ws.cap) {
-    ws.keys[t] = CC_EMPTY;
+    ws.keys[t] = KEY_EMPTY;
     ws.count[t] = 0u;
   }
   if (t < F) {
@@ -70,40 +69,22 @@ __global__ __launch_bounds__(CC_BLOCK) void cc_init_kernel(CcWs ws, uint32_t F, 
   if (t < 2) status[t] = 0u;
 }
 
-__device__ __forceinline__ uint32_t edge_slot(uint64_t key, uint32_t cap) {
-  uint64_t h = key;                                              // murmur3's 64-bit finaliser
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return (uint32_t)(((h >> 32) * cap) >> 32);                    // [0, cap)
-}
-
 __global__ __launch_bounds__(CC_BLOCK) void cc_edges_kernel(const int32_t* __restrict__ faces, uint32_t F, uint32_t V, CcWs ws,
                                                             uint32_t* __restrict__ status) {
   const uint32_t e = blockIdx.x * CC_BLOCK + threadIdx.x;
   if (e >= 3u * F) return;
-  const uint32_t f = e / 3u, k = e - 3u * f;
-  const uint32_t a = (uint32_t)faces[3 * (size_t)f + k], b = (uint32_t)faces[3 * (size_t)f + (k == 2u ? 0u : k + 1u)];
-  const uint32_t c = (uint32_t)faces[3 * (size_t)f + (k == 0u ? 2u : k - 1u)];
-  if (a >= V || b >= V || c >= V) {                              // negative indices are >= 2^31 here: the whole face is out
-    if (k == 0u) atomicOr(&status[1], CC_BAD_INDEX);
+  const FaceEdge q = face_edge(faces, e);
+  if (!face_in_range(faces, q, V)) {
+    if (q.k == 0u) atomicOr(&status[1], CC_BAD_INDEX);
     return;
   }
-  const uint64_t key = ((uint64_t)min(a, b) << 32) | (uint64_t)max(a, b);
-  uint32_t s = edge_slot(key, ws.cap);
-  for (uint32_t probe = 0; probe < ws.cap; ++probe) {
-    uint64_t cur = __hip_atomic_load(&ws.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == CC_EMPTY) cur = atomicCAS((unsigned long long*)&ws.keys[s], (unsigned long long)CC_EMPTY, (unsigned long long)key);
-    if (cur == CC_EMPTY || cur == key) {
-      const uint32_t n = atomicAdd(&ws.count[s], 1u);
-      if (n < 2u) ws.holder[2 * (size_t)s + n] = (int32_t)f;
-      return;
-    }
-    s = s + 1u == ws.cap ? 0u : s + 1u;
+  const uint32_t s = key_claim(ws.keys, ws.cap, edge_key(q.a, q.b), ws.cap);
+  if (s == KEY_NONE) {
+    atomicOr(&status[1], CC_TABLE_FULL);
+    return;
   }
-  atomicOr(&status[1], CC_TABLE_FULL);
+  const uint32_t n = atomicAdd(&ws.count[s], 1u);
+  if (n < 2u) ws.holder[2 * (size_t)s + n] = (int32_t)q.f;
 }
 
 __device__ __forceinline__ int32_t cc_find(int32_t* parent, int32_t x) {

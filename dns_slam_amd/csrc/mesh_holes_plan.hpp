@@ -16,7 +16,7 @@ namespace dns {
 namespace holesp {
 
 constexpr uint32_t HOLES_BLOCK = 256;              // threads per workgroup of every kernel but the carry scan
-constexpr uint32_t SCAN_THREADS = 1024;            // the one workgroup that scans the carries
+using dns::SCAN_THREADS;                           // ws_carve.hpp: the one workgroup that scans the carries
 constexpr uint32_t MAX_FACES = 1u << 29;           // refused from here on: 4 F slots and 3 F + 2 face-edge ids stay below 2^31
 constexpr uint32_t MAX_VERTS = 1u << 31;           // vertex indices are non-negative int32
 constexpr uint32_t MIN_EDGES = 3, MAX_EDGES = 32;  // bounds of max_edges

@@ -7,7 +7,7 @@
 //                   0 < depth < 1000.  The float64 back-projection p = pose (x, y, z, 1) touches the units floor((p - trunc) / L)
 //                   .. floor((p + trunc) / L) per axis (L = 16 voxel_length; 2 trunc < L is required, so at most 2 x 2 x 2).  Each
 //                   (unit, frame) is a 64-bit key claimed in an open-addressing set by compare-and-swap against the all-ones
-//                   word (mesh_cc.hip's cc_edges_kernel); a probe sequence that runs out sets status[0] and the caller retries
+//                   word (dev_keytable.hpp's key_claim); a probe sequence that runs out sets status[0] and the caller retries
 //                   with a larger table -- nothing is dropped silently.  The caller compacts and sorts the keys: that is the
 //                   sorted unit list and, per unit, its frames in ascending order.
 //   tsdf_integrate: workgroup = unit, thread = one (x, y) column of 16 voxels kept in registers, looping over the unit's frames in
@@ -18,6 +18,8 @@
 //                   cubes around that edge has eight observed corners.  Count -> caller's exclusive prefix over units -> emit; a
 //                   workgroup scan orders the vertices by voxel ((x 16 + y) 16 + z), then axis.
 #include "common.hpp"
+#include "dev_keytable.hpp"
+#include "dev_reduce.hpp"
 
 namespace dns {
 
@@ -27,17 +29,6 @@ constexpr int TS_BLOCK = 256;
 constexpr int TS_UNIT = 16;
 constexpr int TS_TILE = TS_UNIT + 2;
 constexpr int TS_MAX_PROBE = 4096;
-constexpr uint64_t TS_EMPTY = ~0ull;
-
-__device__ __forceinline__ uint32_t ts_slot(uint64_t key, uint32_t cap) {
-  uint64_t h = key;                                              // murmur3's 64-bit finaliser
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return (uint32_t)(((h >> 32) * cap) >> 32);
-}
 
 // Signed 64-bit order of the keys = lexicographic order of (ux, uy, uz, frame): ux in two's complement on top, the rest biased.
 __device__ __forceinline__ uint64_t ts_key(int ux, int uy, int uz, uint32_t k) {
@@ -73,22 +64,11 @@ __global__ __launch_bounds__(TS_BLOCK) void tsdf_touch_kernel(const float* __res
     atomicOr(&status[0], 2u);
     return;
   }
+  const uint32_t limit = cap < (uint32_t)TS_MAX_PROBE ? cap : (uint32_t)TS_MAX_PROBE;
   for (int c = 0; c < 8; ++c) {
     if (((c & 1) && hi[0] == lo[0]) || ((c & 2) && hi[1] == lo[1]) || ((c & 4) && hi[2] == lo[2])) continue;
     const uint64_t key = ts_key((c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2], k);
-    uint32_t s = ts_slot(key, cap);
-    bool placed = false;
-    const uint32_t limit = cap < (uint32_t)TS_MAX_PROBE ? cap : (uint32_t)TS_MAX_PROBE;
-    for (uint32_t probe = 0; probe < limit; ++probe) {
-      uint64_t cur = __hip_atomic_load(&table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (cur == TS_EMPTY) cur = atomicCAS((unsigned long long*)&table[s], (unsigned long long)TS_EMPTY, (unsigned long long)key);
-      if (cur == TS_EMPTY || cur == key) {
-        placed = true;
-        break;
-      }
-      s = s + 1u == cap ? 0u : s + 1u;
-    }
-    if (!placed) {
+    if (key_claim(table, cap, key, limit) == KEY_NONE) {
       atomicOr(&status[0], 1u);
       return;
     }
@@ -222,19 +202,12 @@ __global__ __launch_bounds__(TS_BLOCK) void tsdf_vertices_kernel(const int32_t* 
     mask[z] = m;
     n += (uint32_t)__popc(m);
   }
-  scan[threadIdx.x] = n;
-  __syncthreads();
-  for (int s = 1; s < TS_BLOCK; s <<= 1) {                       // inclusive scan over the columns, in voxel order
-    const uint32_t add = threadIdx.x >= (uint32_t)s ? scan[threadIdx.x - s] : 0u;
-    __syncthreads();
-    scan[threadIdx.x] += add;
-    __syncthreads();
-  }
+  const uint32_t incl = block_scan_inclusive<TS_BLOCK>(scan, n);  // over the columns, in voxel order
   if (!EMIT) {
-    if (threadIdx.x == TS_BLOCK - 1) count[b] = (int64_t)scan[TS_BLOCK - 1];
+    if (threadIdx.x == TS_BLOCK - 1) count[b] = (int64_t)incl;
     return;
   }
-  uint64_t at = (uint64_t)offset[b] + (scan[threadIdx.x] - n);
+  uint64_t at = (uint64_t)offset[b] + (incl - n);
   for (int z = 0; z < TS_UNIT; ++z) {
     if (!mask[z]) continue;
     const int p = ((x + 1) * TS_TILE + (y + 1)) * TS_TILE + (z + 1);

@@ -10,6 +10,7 @@
 namespace dns {
 
 inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }      // workspaces are carved into 256-byte aligned parts
+constexpr uint32_t SCAN_THREADS = 1024;  // the one workgroup that scans the carries in a workspace (dev_reduce.hpp's carry_scan)
 
 struct WsCarve {
   char* base;                                                    // NULL: size only

@@ -123,6 +123,20 @@ def test_large_torus():
     assert info["loops_filled"] == 2474 and len(added) == 2474
 
 
+def test_carry_scan_runs_of_two():
+    """262401 vertices are 1026 workgroups of 256: every thread of the carry scan covers a run of two.  Lone triangles in the first
+    workgroup, across the workgroups 0 / 1, in the last workgroup of the last full pair and in the two after it; a quad across
+    511 / 512, i.e. across two scan threads."""
+    n = 1024 * 256 + 257
+    q = 512 * 256 - 2
+    faces = [[a, a + 1, a + 2] for a in (0, 255, 1023 * 256 + 100, 1024 * 256 + 10, n - 3)] + [[q, q + 1, q + 2], [q, q + 2, q + 3]]
+    added, info = _assert_equals_ref(np.array(faces, np.int32), n, 4)
+    assert added.tolist() == [[0, 2, 1], [255, 257, 256], [131070, 131072, 131071], [131070, 131073, 131072],
+                              [261988, 261990, 261989], [262154, 262156, 262155], [262398, 262400, 262399]]
+    assert info.pop("faces_added") == 7 and info.pop("loops_filled") == 6 and info.pop("boundary_edges") == 19
+    assert not any(info.values()), info
+
+
 # ---- the mesher -------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def scene():

@@ -70,6 +70,20 @@ def test_marching_cubes_multiblock_256():
     _assert_same_mesh(gv, gf, rv, rf)
 
 
+def test_marching_cubes_scan_runs_of_two():
+    """65 x 64 x 64 points are 1040 count blocks, the smallest grid of this kind at which every thread of the one-workgroup carry
+    scan covers a run of two blocks."""
+    axes = [np.linspace(-1, 1, n) for n in (65, 64, 64)]
+    X, Y, Z = np.meshgrid(*axes, indexing="ij")
+    vol = (0.6 - np.sqrt(X ** 2 + Y ** 2 + Z ** 2)).astype(np.float32)
+    assert (vol.size + 255) // 256 == 1040
+    o, sp = (-1.0, -1.0, -1.0), [float(a[1] - a[0]) for a in axes]
+    rv, rf = mc_ref.marching_cubes(vol, 0.0, o, sp)
+    assert rv.shape == (6832, 3) and rf.shape == (13660, 3)
+    gv, gf = _gpu_mc(vol, o, sp)
+    _assert_same_mesh(gv, gf, rv, rf)
+
+
 def test_marching_cubes_sphere_area():
     n = 128
     ax = np.linspace(-0.5, 0.5, n)
