@@ -58,11 +58,12 @@ struct KernelSpan {
   hipEvent_t e0;
   bool on;
 };
-#define DNS_LAUNCH(kern, grid, block, lds, st, ...)                    \
+#define DNS_LAUNCH_AS(name, kern, grid, block, lds, st, ...)           \
   do {                                                                  \
-    dns::KernelSpan _span(#kern, st);                                   \
+    dns::KernelSpan _span(name, st);                                    \
     hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);        \
   } while (0)
+#define DNS_LAUNCH(kern, ...) DNS_LAUNCH_AS(#kern, kern, __VA_ARGS__)   // timed under the kernel's own name
 // Fill n_words 32-bit words with `value` by a KERNEL.  The library issues no hipMemsetAsync: captured into a hipGraph, memset
 // nodes misbehave on ROCm 7.0.51831 -- after a host synchronisation that follows a replay, later replays no longer clear
 // their destination (found in round 2 with tools/graph_sync_min.py: the sampling step is stable with the per-frame depth

@@ -18,7 +18,8 @@
 //                   does not depend on the order: the image is the same bits for every call and both methods.
 // A triangle with a non-finite vertex (world or camera space) is skipped and flagged; one with n = 0 is skipped.
 //
-// The set-up and the per-pixel expressions are dev_raster.hpp's, shared with the colour rasteriser (mesh_render.hip).
+// The set-up, the per-pixel expressions, the kernels rs_init, rs_setup and rs_large (rs_draw_init, rs_draw_setup, rs_draw_large
+// with the depth sink, timed as rs_*_kernel) and the host walk over them are dev_raster.hpp's, shared with mesh_render.hip.
 //   rs_init:    the image set to +inf, the list counters and the status words cleared.
 //   rs_setup:   thread = (triangle, view).  Camera space, normal, edge vectors; culled when wholly nearer than z_near, beyond
 //               z_far or outside one of the four side planes of the image (tested as half-spaces of camera space, with a pixel
@@ -46,80 +47,12 @@ namespace dns {
 
 namespace {
 
-constexpr uint32_t RS_INF = 0x7f800000u;
-
-// Pixel (row i, column j) of the image img [H,W]; 0 <= i < H and 0 <= j < W by the caller's box.
-__device__ __forceinline__ void rs_pixel(const RsTri& t, const RsCam& cam, int i, int j, uint32_t* __restrict__ img) {
-  float d;
-  if (rs_depth(t, cam, i, j, d)) {
-    uint32_t* p = img + (size_t)i * (size_t)cam.W + (size_t)j;
-    const uint32_t bits = __float_as_uint(d);
-    if (bits < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, bits);
-  }
-}
-
-__global__ __launch_bounds__(RS_BLOCK) void rs_init_kernel(uint32_t* __restrict__ depth, size_t n_words, uint32_t* __restrict__ counters,
-                                                           uint32_t n_counters, uint32_t* __restrict__ status) {
-  const size_t t0 = (size_t)blockIdx.x * RS_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * RS_BLOCK;
-  for (size_t i = t0; i < n_words; i += stride) depth[i] = RS_INF;
-  for (size_t i = t0; i < n_counters; i += stride) counters[i] = 0u;
-  if (t0 < 4) status[t0] = 0u;
-}
-
-__global__ __launch_bounds__(RS_BLOCK) void rs_setup_kernel(const float* __restrict__ verts, uint32_t P, const int32_t* __restrict__ faces,
-                                                            uint32_t f_lo, uint32_t f_hi, const float* __restrict__ w2c, uint32_t v_lo,
-                                                            RsCam cam, uint32_t flags, uint64_t* __restrict__ list, uint32_t cap,
-                                                            uint32_t* __restrict__ counter, uint32_t* __restrict__ depth,
-                                                            uint32_t* __restrict__ status) {
-  const uint32_t f = f_lo + blockIdx.x * RS_BLOCK + threadIdx.x, view = v_lo + blockIdx.y;
-  if (f >= f_hi) return;
-  RsTri t;
-  if (!rs_setup(verts, P, faces, f, w2c + (size_t)view * 16, cam, t, status)) return;
-  uint32_t* img = depth + (size_t)view * (size_t)cam.H * (size_t)cam.W;
-  const int bw = t.x1 - t.x0 + 1, bh = t.y1 - t.y0 + 1;
-  if (flags & DNS_RASTER_SIMPLE) {
-    for (int i = t.y0; i <= t.y1; ++i)
-      for (int j = t.x0; j <= t.x1; ++j) rs_pixel(t, cam, i, j, img);
-    if (flags & DNS_RASTER_STATS) atomicAdd(&status[2], 1u);
-  } else if (bw <= RS_SMALL && bh <= RS_SMALL) {
-    for (int a = 0; a < RS_SMALL; ++a)
-      for (int b = 0; b < RS_SMALL; ++b)
-        if (a < bh && b < bw) rs_pixel(t, cam, t.y0 + a, t.x0 + b, img);
-    if (flags & DNS_RASTER_STATS) atomicAdd(&status[2], 1u);
-  } else {
-    const uint32_t pos = atomicAdd(counter, 1u);
-    if (pos < cap) list[pos] = ((uint64_t)view << 32) | (uint64_t)f;      // cap >= the pairs of this launch: always
-  }
-}
-
-__global__ __launch_bounds__(RS_BLOCK) void rs_large_kernel(const float* __restrict__ verts, uint32_t P, const int32_t* __restrict__ faces,
-                                                            uint32_t F, const float* __restrict__ w2c, uint32_t V, RsCam cam,
-                                                            const uint64_t* __restrict__ list, uint32_t cap,
-                                                            const uint32_t* __restrict__ counter, uint32_t* __restrict__ depth,
-                                                            uint32_t* __restrict__ status) {
-  const uint32_t n = min(*counter, cap);
-  for (uint32_t e = blockIdx.x; e < n; e += gridDim.x) {
-    const uint64_t ent = list[e];
-    const uint32_t f = (uint32_t)ent, view = (uint32_t)(ent >> 32);
-    if (f >= F || view >= V) continue;
-    RsTri t;
-    if (!rs_setup(verts, P, faces, f, w2c + (size_t)view * 16, cam, t, status)) continue;
-    uint32_t* img = depth + (size_t)view * (size_t)cam.H * (size_t)cam.W;
-    const uint32_t bw = (uint32_t)(t.x1 - t.x0 + 1), area = bw * (uint32_t)(t.y1 - t.y0 + 1);
-    for (uint32_t p = threadIdx.x; p < area; p += RS_BLOCK) rs_pixel(t, cam, t.y0 + (int)(p / bw), t.x0 + (int)(p % bw), img);
-  }
-}
-
 __global__ __launch_bounds__(RS_BLOCK) void rs_finish_kernel(uint32_t* __restrict__ depth, size_t n_words, const uint32_t* __restrict__ counters,
                                                              uint32_t n_counters, uint32_t* __restrict__ status) {
   const size_t t0 = (size_t)blockIdx.x * RS_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * RS_BLOCK;
   for (size_t i = t0; i < n_words; i += stride)
-    if (depth[i] == RS_INF) depth[i] = 0u;
-  if (t0 == 0) {
-    uint32_t s = 0;
-    for (uint32_t k = 0; k < n_counters; ++k) s += counters[k];
-    status[1] = s;
-  }
+    if (depth[i] == RsDepthSink::EMPTY) depth[i] = 0u;
+  if (t0 == 0) status[1] = rs_list_total(counters, n_counters);
 }
 
 // ---- depth L1 --------------------------------------------------------------------------------------------------------------
@@ -199,41 +132,21 @@ extern "C" uint64_t dns_rasterize_ws_bytes(uint32_t F, uint32_t V, uint32_t H, u
 extern "C" int dns_rasterize_depth(const float* verts, uint32_t P, const int32_t* faces, uint32_t F, const float* w2c, uint32_t V,
                                    uint32_t H, uint32_t W, const float* intr, float z_near, float z_far, uint32_t flags,
                                    uint32_t list_cap, void* ws, float* depth, uint32_t* status, void* stream) {
-  DNS_REQUIRE(F < (1u << 31) && P < (1u << 31), "dns_rasterize_depth: %u vertices, %u faces (must be < 2^31)", P, F);
-  DNS_REQUIRE(H > 0 && W > 0 && H <= 32768u && W <= 32768u, "dns_rasterize_depth: image %u x %u", H, W);
   DNS_REQUIRE((flags & ~(DNS_RASTER_SIMPLE | DNS_RASTER_STATS)) == 0u, "dns_rasterize_depth: unknown flags %#x", flags);
-  DNS_REQUIRE(z_near > 0.f && z_far >= z_near && z_far <= 3.0e38f, "dns_rasterize_depth: z_near %g, z_far %g (need 0 < z_near <= z_far, finite)",
-              (double)z_near, (double)z_far);
+  RsCam cam;
+  RsCut cut;
+  if (const int e = rs_check("dns_rasterize_depth", P, F, V, H, W, intr, z_near, z_far, list_cap, &cam, &cut)) return e;
   if (V == 0) return DNS_OK;
-  DNS_REQUIRE(intr && w2c && ws && depth && status, "dns_rasterize_depth: NULL argument");
+  DNS_REQUIRE(w2c && ws && depth && status, "dns_rasterize_depth: NULL argument");
   DNS_REQUIRE(F == 0 || (verts && faces), "dns_rasterize_depth: F > 0 needs verts and faces");
-  DNS_REQUIRE(intr[0] - intr[0] == 0.f && intr[1] - intr[1] == 0.f && intr[0] != 0.f && intr[1] != 0.f && intr[2] - intr[2] == 0.f &&
-                  intr[3] - intr[3] == 0.f, "dns_rasterize_depth: intrinsics must be finite, fx and fy non-zero");
-  const auto [cap, r, g, n_launch] = rs_cut(F, V, list_cap);
-  DNS_REQUIRE(n_launch <= RS_MAX_LAUNCHES, "dns_rasterize_depth: list_cap %u cuts %u faces x %u views into %llu launches (at most %u)",
-              list_cap, F, V, (unsigned long long)n_launch, RS_MAX_LAUNCHES);
   hipStream_t st = (hipStream_t)stream;
   RsWs w;
   rs_layout(ws, 0, F, V, &w);
   uint32_t* img = (uint32_t*)depth;
   const size_t n_words = (size_t)V * H * W;
-  const RsCam cam = {intr[0], intr[1], intr[2], intr[3], z_near, z_far, (int)H, (int)W};
-  const uint32_t fill_grid = (uint32_t)std::min<size_t>(8192, (n_words + RS_BLOCK - 1) / RS_BLOCK);
-  DNS_LAUNCH(rs_init_kernel, dim3(std::max(fill_grid, (uint32_t)((n_launch + RS_BLOCK - 1) / RS_BLOCK))), dim3(RS_BLOCK), 0, st, img,
-             n_words, w.counters, (uint32_t)n_launch, status);
-  uint32_t k = 0;
-  for (uint32_t v_lo = 0; F && v_lo < V; v_lo += g) {
-    const uint32_t nv = std::min(g, V - v_lo);
-    for (uint32_t f_lo = 0; f_lo < F; f_lo += r, ++k) {
-      const uint32_t f_hi = std::min(F, f_lo + r);
-      DNS_LAUNCH(rs_setup_kernel, dim3((f_hi - f_lo + RS_BLOCK - 1) / RS_BLOCK, nv), dim3(RS_BLOCK), 0, st, verts, P, faces, f_lo, f_hi,
-                 w2c, v_lo, cam, flags, w.list, cap, w.counters + k, img, status);
-      if (!(flags & DNS_RASTER_SIMPLE))
-        DNS_LAUNCH(rs_large_kernel, dim3(RS_LARGE_GRID), dim3(RS_BLOCK), 0, st, verts, P, faces, F, w2c, V, cam, (const uint64_t*)w.list,
-                   cap, (const uint32_t*)(w.counters + k), img, status);
-    }
-  }
-  DNS_LAUNCH(rs_finish_kernel, dim3(fill_grid), dim3(RS_BLOCK), 0, st, img, n_words, (const uint32_t*)w.counters, (uint32_t)n_launch, status);
+  rs_draw<RsDepthSink>(verts, P, faces, F, w2c, V, cam, flags, cut, w, img, status, st);
+  DNS_LAUNCH(rs_finish_kernel, dim3(rs_fill_grid(n_words)), dim3(RS_BLOCK), 0, st, img, n_words, (const uint32_t*)w.counters,
+             (uint32_t)cut.n_launch, status);
   return check_launch("dns_rasterize_depth");
 }
 

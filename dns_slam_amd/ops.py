@@ -1681,19 +1681,25 @@ def _check_face_indices(f, P):
             raise ValueError(f"rasterize_depth: a face holds a vertex index outside [0, {P}) (min {lo}, max {hi})")
 
 
-def rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near=0.01, z_far=20.0, method="auto", stats=False,
-                           list_cap=0):
-    """``rasterize_depth`` without its host reads: -> (depth [V,H,W] fp32, status [4] int32 on the device; include/dns_hip.h).
-    The face indices are NOT validated here (a face with an index outside [0, P) is skipped by the kernel and flagged in
-    status[0] bit 1); int64 faces must fit int32.  ``list_cap``: pairs per launch (0: the library's default)."""
+def _raster_launch_arguments(who, check_indices, verts, faces, w2c, H, W, fx, fy, cx, cy, z_near, z_far, method, stats):
+    """The arguments the two rasterisers share, validated once, ``who`` naming the caller in the camera messages: -> (v, f as
+    int32, w, z_near, z_far, P, F, V, the flag bits of ``method`` and ``stats``).  ``check_indices``: the checked entry points'
+    host read of the face indices, made before anything is allocated or launched."""
     v, f, w = _raster_arguments(verts, faces, w2c, H, W, method)
-    f = f.to(torch.int32)
+    if check_indices:
+        _check_face_indices(f, int(v.shape[0]))
     zn, zf = float(z_near), float(z_far)
     if not (zn > 0.0 and zf >= zn and math.isfinite(zf)):
-        raise ValueError(f"rasterize_depth: need 0 < z_near <= z_far < inf, got {z_near!r}, {z_far!r}")
+        raise ValueError(f"{who}: need 0 < z_near <= z_far < inf, got {z_near!r}, {z_far!r}")
     if not (all(math.isfinite(float(x)) for x in (fx, fy, cx, cy)) and float(fx) != 0.0 and float(fy) != 0.0):
-        raise ValueError("rasterize_depth: the intrinsics must be finite, fx and fy non-zero")
-    P, F, V = int(v.shape[0]), int(f.shape[0]), int(w.shape[0])
+        raise ValueError(f"{who}: the intrinsics must be finite, fx and fy non-zero")
+    flags = (1 if method == "simple" else 0) | (2 if stats else 0)
+    return v, f.to(torch.int32), w, zn, zf, int(v.shape[0]), int(f.shape[0]), int(w.shape[0]), flags
+
+
+def _rasterize_depth(check_indices, verts, faces, w2c, H, W, fx, fy, cx, cy, z_near, z_far, method, stats, list_cap):
+    v, f, w, zn, zf, P, F, V, flags = _raster_launch_arguments("rasterize_depth", check_indices, verts, faces, w2c, H, W, fx, fy, cx, cy,
+                                                               z_near, z_far, method, stats)
     dev = v.device
     depth = torch.empty(V, int(H), int(W), dtype=torch.float32, device=dev)
     status = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -1701,10 +1707,17 @@ def rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near=0.01,
         return depth, status
     ws = _byte_workspace(_rawlib.dns_rasterize_ws_bytes(F, V, int(H), int(W)), dev,
                          f"rasterize_depth: {F} faces at {H} x {W} are refused (F >= 2^31)")
-    flags = (1 if method == "simple" else 0) | (2 if stats else 0)
     check(lib.dns_rasterize_depth(ptr(v), P, ptr(f), F, ptr(w), V, int(H), int(W), _intrinsics(fx, fy, cx, cy), zn, zf, flags, int(list_cap), ptr(ws),
                                   ptr(depth), ptr(status), stream_ptr()), "dns_rasterize_depth")
     return depth, status
+
+
+def rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near=0.01, z_far=20.0, method="auto", stats=False,
+                           list_cap=0):
+    """``rasterize_depth`` without its host reads: -> (depth [V,H,W] fp32, status [4] int32 on the device; include/dns_hip.h).
+    The face indices are NOT validated here (a face with an index outside [0, P) is skipped by the kernel and flagged in
+    status[0] bit 1); int64 faces must fit int32.  ``list_cap``: pairs per launch (0: the library's default)."""
+    return _rasterize_depth(False, verts, faces, w2c, H, W, fx, fy, cx, cy, z_near, z_far, method, stats, list_cap)
 
 
 def rasterize_depth(verts: torch.Tensor, faces: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: float, fy: float, cx: float,
@@ -1717,9 +1730,7 @@ def rasterize_depth(verts: torch.Tensor, faces: torch.Tensor, w2c: torch.Tensor,
     (every triangle by its set-up thread).  A face index outside [0, P) and CPU tensors raise ValueError (one host read for the
     indices).  ``return_stats`` appends {"nonfinite": a triangle with a non-finite vertex was skipped, "large": (triangle, view)
     pairs drawn through the list, "small": pairs drawn by their set-up thread} (a second host read)."""
-    v, f, _ = _raster_arguments(verts, faces, w2c, H, W, method)
-    _check_face_indices(f, int(v.shape[0]))
-    depth, status = rasterize_depth_launch(verts, faces, w2c, H, W, fx, fy, cx, cy, z_near, z_far, method, stats=return_stats)
+    depth, status = _rasterize_depth(True, verts, faces, w2c, H, W, fx, fy, cx, cy, z_near, z_far, method, return_stats, 0)
     if not return_stats:
         return depth
     bad, large, small, _ = (int(x) for x in status.cpu().tolist())
@@ -1777,19 +1788,11 @@ def _render_colors(who, what, colors, n, dev):
     return c
 
 
-def render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, *, z_near=0.01, z_far=20.0, cull=None, shade=None,
-                       ambient=0.3, background=(1, 1, 1), points=None, point_colors=None, point_size=4, method="auto",
-                       list_cap=None, stats=False):
-    """``render_mesh`` without its host read: the face indices are NOT validated (a face with an index outside [0, P) is skipped
-    by the kernel and flagged in status[0] bit 1); int64 faces must fit int32."""
+def _render_mesh(check_indices, verts, faces, colors, w2c, H, W, fx, fy, cx, cy, *, z_near, z_far, cull, shade, ambient, background,
+                 points, point_colors, point_size, method, list_cap, stats):
     who = "render_mesh"
-    v, f, w = _raster_arguments(verts, faces, w2c, H, W, method)
-    f = f.to(torch.int32)
-    zn, zf = float(z_near), float(z_far)
-    if not (zn > 0.0 and zf >= zn and math.isfinite(zf)):
-        raise ValueError(f"{who}: need 0 < z_near <= z_far < inf, got {z_near!r}, {z_far!r}")
-    if not (all(math.isfinite(float(x)) for x in (fx, fy, cx, cy)) and float(fx) != 0.0 and float(fy) != 0.0):
-        raise ValueError(f"{who}: the intrinsics must be finite, fx and fy non-zero")
+    v, f, w, zn, zf, P, F, V, flags = _raster_launch_arguments(who, check_indices, verts, faces, w2c, H, W, fx, fy, cx, cy, z_near,
+                                                               z_far, method, stats)
     if cull not in RENDER_CULL:
         raise ValueError(f"{who}: cull must be one of {RENDER_CULL}, got {cull!r}")
     if shade not in RENDER_SHADE:
@@ -1802,7 +1805,6 @@ def render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, *, z_nea
     bg = tuple(float(x) for x in background)
     if len(bg) != 3 or not all(math.isfinite(x) for x in bg):
         raise ValueError(f"{who}: background must be three finite numbers, got {background!r}")
-    P, F, V = int(v.shape[0]), int(f.shape[0]), int(w.shape[0])
     dev = v.device
     col = _render_colors(who, "colors", colors, P, dev)
     if (points is None) != (point_colors is None):
@@ -1824,12 +1826,22 @@ def render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, *, z_nea
     if V == 0:
         return out
     ws = _byte_workspace(_rawlib.dns_render_mesh_ws_bytes(F, V, H, W), dev, f"{who}: {F} faces at {H} x {W} are refused (F >= 2^31)")
-    flags = (1 if method == "simple" else 0) | (2 if stats else 0) | _RENDER_CULL_FLAGS[cull] | (_RENDER_HEADLIGHT if shade else 0)
+    flags |= _RENDER_CULL_FLAGS[cull] | (_RENDER_HEADLIGHT if shade else 0)
     check(lib.dns_render_mesh(ptr(v), P, ptr(f), F, ptr(col), ptr(pts), ptr(pcol), N, int(point_size), ptr(w), V, H, W,
                               _intrinsics(fx, fy, cx, cy), zn, zf, flags, amb, (C.c_float * 3)(*bg), int(list_cap or 0), ptr(ws),
                               ptr(out["color"]), ptr(out["depth"]), ptr(out["index"]), ptr(out["status"]), stream_ptr()),
           "dns_render_mesh")
     return out
+
+
+def render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, *, z_near=0.01, z_far=20.0, cull=None, shade=None,
+                       ambient=0.3, background=(1, 1, 1), points=None, point_colors=None, point_size=4, method="auto",
+                       list_cap=None, stats=False):
+    """``render_mesh`` without its host read: the face indices are NOT validated (a face with an index outside [0, P) is skipped
+    by the kernel and flagged in status[0] bit 1); int64 faces must fit int32."""
+    return _render_mesh(False, verts, faces, colors, w2c, H, W, fx, fy, cx, cy, z_near=z_near, z_far=z_far, cull=cull, shade=shade,
+                        ambient=ambient, background=background, points=points, point_colors=point_colors, point_size=point_size,
+                        method=method, list_cap=list_cap, stats=stats)
 
 
 def render_mesh(verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor, w2c: torch.Tensor, H: int, W: int, fx: float,
@@ -1851,11 +1863,9 @@ def render_mesh(verts: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor, 
     thread (with ``stats``).  The arithmetic is written out in include/dns_hip.h.  A face index outside [0, P), CPU tensors,
     colours that are not fp32 [P,3] / [N,3], an unknown ``cull``, ``shade`` or ``method``, ``point_size`` outside 1..16 and
     ``ambient`` outside [0, 1] raise ValueError (one host read for the indices)."""
-    v, f, _ = _raster_arguments(verts, faces, w2c, H, W, method)
-    _check_face_indices(f, int(v.shape[0]))
-    return render_mesh_launch(verts, faces, colors, w2c, H, W, fx, fy, cx, cy, z_near=z_near, z_far=z_far, cull=cull, shade=shade,
-                              ambient=ambient, background=background, points=points, point_colors=point_colors,
-                              point_size=point_size, method=method, list_cap=list_cap, stats=stats)
+    return _render_mesh(True, verts, faces, colors, w2c, H, W, fx, fy, cx, cy, z_near=z_near, z_far=z_far, cull=cull, shade=shade,
+                        ambient=ambient, background=background, points=points, point_colors=point_colors, point_size=point_size,
+                        method=method, list_cap=list_cap, stats=stats)
 
 
 # ----------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)
